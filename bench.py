@@ -159,6 +159,23 @@ def cpu_baseline(model, hp, kw, executed_full: float, threads: int, budget_s: fl
                       f"executes per full-size gene"}
 
 
+DUMP_CAP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: the arrays the timed path returned in its last step, as <out_dir>/<name>.npy in float32, so that two
+    builds can be compared output for output on identical inputs.  An array larger than its share of the 64 MiB cap is
+    written as a fixed, seeded sample of its rows (the same rows for the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_CAP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            rows = np.random.default_rng(0).choice(len(a), share // a[0].nbytes, replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as sk:
@@ -238,6 +255,8 @@ def run_stub(args, rank, world, use_dist):
     dt, expr = timed_steps(step, args.steps, args.warmup, use_dist, lambda: None, dev)
     want = torch.tensor([[g * 100.0 + t for t in range(T)] for g in range(world * G)], dtype=torch.float32)
     assert torch.equal(expr, want), "gathered matrix is not in query order"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"expression": expr})
     if rank == 0:
         print(json.dumps({"metric": "genes/sec/node (54-tissue expr) at 1 Mb cis-window", "value": round(world * G * args.steps / dt, 4),
                           "unit": "genes/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -247,8 +266,9 @@ def run_stub(args, rank, world, use_dist):
                                      "parallelism": f"gene-shard x{world}"}}))
 
 
-def cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, steps: int, warmup: int) -> dict:
-    """One strong-scaling measurement on BASELINE configs[2] (256 ragged genes, LPT shards, one gather per pass)."""
+def cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, steps: int, warmup: int):
+    """One strong-scaling measurement on BASELINE configs[2] (256 ragged genes, LPT shards, one gather per pass): the
+    [256, T] expression matrix of the last pass and the record of the measurement."""
     import torch.distributed as dist
     from variantformer_amd.dist import all_gather_expression, gene_cost, shard_genes_lpt
     from variantformer_amd.utils.flops import batch_flops
@@ -293,7 +313,7 @@ def cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, steps: int, warmu
             flops_all = float(sum(float(x[1]) for x in allt))
         assert torch.isfinite(expr).all() and tuple(expr.shape) == (n_genes, T)
     loads = [sum(costs[i] for i in o) for o in owned]
-    return {"value": round(n_genes * steps / dt, 4), "unit": "genes/sec", "scaling": "strong", "steps": steps, "warmup": warmup,
+    return expr, {"value": round(n_genes * steps / dt, 4), "unit": "genes/sec", "scaling": "strong", "steps": steps, "warmup": warmup,
             "ms_per_pass": round(dt / steps * 1e3, 3), "genes": n_genes, "batch_genes_per_launch": bs, "tissues": T,
             "algorithmic_tflop_per_pass": round(flops_all / 1e12, 2),
             "achieved_algorithmic_tflops_whole_step": round(flops_all * steps / dt / 1e12, 1),
@@ -306,7 +326,9 @@ def cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, steps: int, warmu
 def run_cfg3(args, model, hp, kw, dev, rank, world, use_dist):
     """--workload cfg3: the line's `value` is the strong-scaling pass over BASELINE configs[2]."""
     import torch.distributed as dist
-    r = cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, args.steps, args.warmup)
+    expr, r = cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"expression": expr})
     if rank == 0:
         T = args.tissues
         print(json.dumps({
@@ -431,8 +453,14 @@ def main():
                     help="runtime.Switches.overlap_cre_stream off for the whole run (the order the per-kernel replay uses): what "
                          "the rocprofv3 --kernel-trace --stats pass profiles, because with two streams a kernel's traced "
                          "duration includes the time it shares the CUs with the other stream's kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32, rank 0: the "
+                         "gathered expression matrix, and for cfg2 the embeddings of rank 0's genes; at most 64 MiB, a "
+                         "seeded row sample beyond that); the inputs are the same in every run with the same flags")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)      # launcher test: no model, gloo on CPU
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:        # no launcher around us: start the ranks as a child process
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -511,10 +539,13 @@ def main():
             extra_warmup += 1
             still_allocating = n_alloc() != before
 
-        dt, (expr, _) = timed_steps(step, args.steps, 0, use_dist, torch.cuda.synchronize, dev)
+        dt, (expr, emb) = timed_steps(step, args.steps, 0, use_dist, torch.cuda.synchronize, dev)
         each_step_ms = timed_steps.last_step_ms
         allocs_in_timed_region = timed_steps.device_allocs
         assert torch.isfinite(expr).all() and tuple(expr.shape) == (world * G, len(tissues))
+        if rank == 0 and args.dump_outputs:         # before the passes below reuse the model (trained_like rewrites its weights)
+            dump_outputs(args.dump_outputs, {"expression": expr, "embeddings": emb})
+        del emb
 
         # After the timed region: (1) the same steps on ONE stream (runtime.Switches.overlap_cre_stream off: the product default
         # runs the CRE layers on a side stream beside the gene layers; bit-identical, so max_rel_diff must be 0.0); (2) the
@@ -608,7 +639,7 @@ def main():
         strong = None
         if world > 1 and not args.no_cfg3:
             # the informative multi-GPU number: total work fixed (BASELINE configs[2]), LPT shards, busy time per rank
-            strong = cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, steps=2, warmup=1)
+            _, strong = cfg3_pass(args, model, hp, kw, dev, rank, world, use_dist, steps=2, warmup=1)
         flow = None
         if rank == 0 and world == 1 and not args.no_pipelined:
             flow = pipelined_product_flow(model, batch, max(4, min(args.steps, 10)), dev)

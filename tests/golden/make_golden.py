@@ -472,7 +472,13 @@ def bpe_fixture():
 
 
 def misc_fixture():
-    """ALiBi slopes, sinusoidal PE, precision2dtype and pad/unpad conventions from the reference."""
+    """ALiBi slopes, sinusoidal PE, precision2dtype and pad/unpad conventions from the reference.  Written by a child process
+    on the pinned CPU math path (tests/helpers.PINNED_CPU_MATH): the PE tables are compared bit for bit on any host."""
+    from tests.helpers import PINNED_CPU_MATH
+    if any(os.environ.get(k) != v for k, v in PINNED_CPU_MATH.items()):
+        import subprocess
+        subprocess.run([sys.executable, os.path.abspath(__file__), "misc"], env=dict(os.environ, **PINNED_CPU_MATH), check=True)
+        return
     from seq2gene.modules.layers import get_alibi_slopes
     from seq2reg.model import positionalencoding1d
     from utils.functions import precision2dtype

@@ -32,6 +32,13 @@ def signal_rel(got, want):
     return float(np.abs(g - w).max() / w.std())
 
 
+# The environment of a process whose CPU transcendentals must be bit-identical on every x86-64 host.  torch evaluates
+# exp / sin / cos through MKL's vector math, whose last bits depend on the code path MKL picks for the CPU (an AVX-512
+# Intel host and an AMD host disagree by up to 64 ulps in a 512 x 200 sinusoidal table); MKL's SSE4.2 path runs the same
+# instructions on every such host.  Read at process start, so it applies to child processes only.
+PINNED_CPU_MATH = {"MKL_ENABLE_INSTRUCTIONS": "SSE4_2", "ATEN_CPU_CAPABILITY": "default"}
+
+
 SIGNAL_RTOL = 2e-2      # expression error allowed as a fraction of the across-gene / across-tissue spread (signal_rel);
                         # measured on MI355X: 5e-4 ... 1.5e-2 (profiles/r05_l_pytest_gpu_final.log; 3e-2 until round 6)
 

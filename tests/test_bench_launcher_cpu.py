@@ -28,6 +28,21 @@ def test_self_launch_two_ranks_stub_step():
     assert abs(d["value"] - 2 * 3 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-2      # whole-job aggregate over both ranks
 
 
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the gathered matrix of the last timed step as DIR/expression.npy (float32);
+    --steps below 1 is refused."""
+    import numpy as np
+    r = _run("--gpus", "2", "--steps", "2", "--warmup", "0", "--stub", "--genes-per-step", "3", "--tissues", "5",
+             "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(tmp_path / "out")) == ["expression.npy"]
+    got = np.load(tmp_path / "out" / "expression.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, [[g * 100.0 + t for t in range(5)] for g in range(6)])
+    r = _run("--gpus", "1", "--steps", "0", "--stub")
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_single_process_stub_and_launcher_mismatch():
     r = _run("--gpus", "1", "--steps", "2", "--warmup", "0", "--stub")
     assert r.returncode == 0 and json.loads(r.stdout.strip())["n_gpus"] == 1

@@ -2,12 +2,15 @@
 (tests/golden/make_golden.py; fp32, CPU).  No GPU, no reference checkout needed."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import torch
 
 from oracle import vf_oracle as O
-from tests.conftest import GOLDEN
+from tests.conftest import GOLDEN, REPO
+from tests.helpers import PINNED_CPU_MATH
 
 RTOL = 2e-5   # fp32 round-off between two fp32 CPU evaluations of the same graph
 ATOL = 2e-5
@@ -109,14 +112,20 @@ def test_folded_layernorm_is_the_same_algebra(golden):
         np.testing.assert_allclose(a["pred_gene_exp"][i], arrays[f"pred_gene_exp_{i}"], rtol=3e-2, atol=3e-2)
 
 
-def test_alibi_pe_precision_known_answers():
+def test_alibi_pe_precision_known_answers(tmp_path):
     misc = np.load(os.path.join(GOLDEN, "misc.npz"))
     for h in (2, 4, 8, 12, 32):
         np.testing.assert_allclose(np.array(O.alibi_slopes(h)), misc[f"alibi_{h}"], rtol=1e-6)
     # a-priori known answer: H=32 -> 2^(-(k+1)/4)
     np.testing.assert_allclose(O.alibi_slopes(32), [2 ** (-(k + 1) / 4) for k in range(32)], rtol=1e-12)
-    np.testing.assert_array_equal(O.positional_encoding_1d(128, 40).numpy(), misc["pe_128_40"])
-    np.testing.assert_array_equal(O.positional_encoding_1d(512, 200).numpy(), misc["pe_512_200"])
+    # bit-exact sinusoidal tables: computed, as the golden ones were, in a process on the pinned CPU math path
+    code = ("import sys, numpy as np; sys.path.insert(0, sys.argv[1]); from oracle import vf_oracle as O; "
+            "np.savez(sys.argv[2], **{f'pe_{d}_{n}': O.positional_encoding_1d(d, n).numpy() for d, n in ((128, 40), (512, 200))})")
+    out = os.path.join(tmp_path, "pe.npz")
+    subprocess.run([sys.executable, "-s", "-c", code, REPO, out], env=dict(os.environ, **PINNED_CPU_MATH), check=True, timeout=300)
+    pe = np.load(out)
+    np.testing.assert_array_equal(pe["pe_128_40"], misc["pe_128_40"])
+    np.testing.assert_array_equal(pe["pe_512_200"], misc["pe_512_200"])
     with open(os.path.join(GOLDEN, "misc.json")) as f:
         prec = json.load(f)["precision2dtype"]
     for s, want in prec.items():
