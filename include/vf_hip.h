@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VF_ABI_VERSION 12
+#define VF_ABI_VERSION 13
 
 enum vf_status {
     VF_OK = 0,
@@ -148,7 +148,7 @@ int vf_pack_geglu_rows(const void* W, const float* bias, void* W_out, float* bia
  * (call sites seq2reg/modules.py:167; seq2gene/modules/layers.py:437-439,465,482).
  * q/k/v point at the first head of token 0 (so a packed [tokens,3,H,dh] buffer is passed as
  * q=base, k=base+H*dh, v=base+2*H*dh with row stride 3*H*dh).  bf16 in/out, fp32 softmax and
- * accumulation.  dh in {32, 48, 64}.  cu_seqlens_*: int32 [n_seq+1] device arrays.
+ * accumulation.  dh in {32, 48, 64, 96, 128} (every multiple of 8 up to 256: vf_attn_varlen_fwd_v3).  cu_seqlens_*: int32 [n_seq+1] device arrays.
  * alibi_slopes: fp32 [H] device array or NULL.  Sequences with 0 queries are skipped; the rows of
  * queries whose key sequence is empty are written as zeros (flash-attn's convention). */
 int vf_attn_varlen_fwd(const void* q, const void* k, const void* v, void* out,
@@ -191,6 +191,20 @@ int vf_attn_varlen_fwd_qstart_f16(const void* q, const void* k, const void* v, v
  *                       form: the result never depends on the magnitude of the logits, only the speed of such a block. */
 enum vf_attn_flags { VF_ATTN_Q_AT_START = 1, VF_ATTN_Q_LOG2 = 2 };
 int vf_attn_varlen_fwd_v2(const void* q, const void* k, const void* v, void* out,
+                          int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride,
+                          const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                          int n_seq, int max_seqlen_q, int max_seqlen_k,
+                          int H, int dh, const float* alibi_slopes, float scale,
+                          int operand_dtype, int flags, void* stream);
+
+/* Every head dim flash-attn takes (ABI 13): vf_attn_varlen_fwd_v2's arguments and semantics, with dh any multiple of 8 in
+ * [8, 256]; any other dh is refused (VF_ERR_INVALID_ARG, "head_dim" in vf_last_error()) before anything is launched.
+ * dh in {32, 48, 64, 96, 128} runs exactly vf_attn_varlen_fwd_v2's dispatch (bit-identical results).  Any other dh runs the
+ * kernels of its class, told the true dh: 8-32 -> 32, 40 -> 48, 56 -> 64, 72-96 -> 96, 104-128 -> 128, 136-192 -> 192,
+ * 200-256 -> 256.  The loads leave zeros in the class's columns past dh and only columns < dh are written, so the result
+ * equals, bit for bit, a class-dh call on operands zero-padded per head (same scale and flags).  Padded head dims have no
+ * row-map form (vf_attn_rows_supported returns 0 for them). */
+int vf_attn_varlen_fwd_v3(const void* q, const void* k, const void* v, void* out,
                           int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride,
                           const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
                           int n_seq, int max_seqlen_q, int max_seqlen_k,

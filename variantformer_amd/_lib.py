@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libvf_hip.so")
 # enums of include/vf_hip.h
 VF_F32, VF_BF16, VF_F16 = 0, 1, 2
 EPI_BF16, EPI_F32, EPI_RES_F32, EPI_GEGLU_BF16, EPI_GELU_F32, EPI_GELU_BF16 = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -41,6 +41,7 @@ SIGNATURES = {
     "vf_attn_varlen_fwd_f16": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
     "vf_attn_varlen_fwd_qstart_f16": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
     "vf_attn_varlen_fwd_v2": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p],
+    "vf_attn_varlen_fwd_v3": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p],
     "vf_attn_rows_supported": [_i, _i, _i, _i, _i, _i, _i],
     "vf_attn_counted_keys": [_p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],
     "vf_softmax_counted": [_p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],

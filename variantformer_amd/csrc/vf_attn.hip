@@ -19,6 +19,12 @@
 //                  16+4g+(j-4) for j>=4) identically on both operands, so no lane movement is needed.
 // dh = 48 (the modulator's 1536/32) is padded to 64 only along the QK^T contraction (zero chunks in
 // the K tile and zero Q fragments); PV uses exactly dh/16 output tiles.
+//
+// Head-dim classes (vf_attn_varlen_fwd_v3): every multiple of 8 up to 256 runs the kernels of the smallest class
+// (32 / 48 / 64 / 96 / 128 / 192 / 256) that holds it, instantiated with PAD = true and told the true dh at run time
+// (AttnParamsPad::dh): loads fetch dh / 8 chunks per row and leave zeros in the class's remaining Q / K / V columns, stores write
+// the columns < dh.  The arithmetic is the class's: the result equals, bit for bit, a class-dh call on operands whose head
+// columns were zero-padded.  The PAD = false instantiations (the five class head dims themselves) never read AttnParamsPad::dh.
 #include <stdlib.h>
 #include <type_traits>
 #include "vf_common.h"
@@ -28,16 +34,17 @@ namespace {
 constexpr int BKV = 64;
 
 // K tile: one row per key, the head dimension padded to 64 (dh <= 64: 128-byte rows, 8 chunks of 16 bytes) or to 128
-// (dh = 96 / 128: 256-byte rows, 16 chunks).  Chunk c of row `row` is stored at chunk c ^ swz(row), which makes the
-// ds_read_b128 of a 16-lane group (rows r = 0..15, same logical chunk) hit 16 distinct 16-byte bank slots:
-// 128-byte rows alternate between the two halves of the 256-byte bank row, so 8 XOR values suffice; 256-byte rows all
-// start on the same bank and need all 16.
+// (dh = 96 / 128: 256-byte rows, 16 chunks); the classes 192 / 256 keep their width (384- / 512-byte rows, 24 / 32 chunks).
+// Chunk c of row `row` is stored at chunk c ^ swz(row), which makes the ds_read_b128 of a 16-lane group (rows r = 0..15,
+// same logical chunk) hit 16 distinct 16-byte bank slots: 128- and 384-byte rows alternate between the two halves of the
+// 256-byte bank row, so 8 XOR values suffice (they only touch the low 3 bits of c: c ^ swz stays inside the row); 256- and
+// 512-byte rows all start on the same bank and need all 16.
 template <int DH>
 struct KLayout {
-    static constexpr int ROW = DH <= 64 ? 128 : 256;
+    static constexpr int ROW = DH <= 64 ? 128 : DH <= 128 ? 256 : DH * 2;
     static constexpr int TILE = BKV * ROW;
     static constexpr int KS = DH <= 64 ? 2 : DH / 32;            // 32-deep MFMA steps of the QK^T contraction
-    static __device__ __forceinline__ int swz(int row) { return ROW == 128 ? (row >> 1) & 7 : row & 15; }
+    static __device__ __forceinline__ int swz(int row) { return (ROW == 128 || ROW == 384) ? (row >> 1) & 7 : row & 15; }
 };
 
 template <int DH>
@@ -102,6 +109,15 @@ struct AttnParams {
 #endif
 };
 
+// The padded-class kernels' argument (PAD = true): AttnParams plus the true head dim, a multiple of 8 below the class DH.  A
+// type of its own, so that the arguments -- and the code -- of the class instantiations stay exactly what they were.
+struct AttnParamsPad : AttnParams {
+    int dh;
+};
+template <bool PAD> using AttnArgs = typename std::conditional<PAD, AttnParamsPad, AttnParams>::type;
+// the kernels' `const int dh = PAD ? pad_dh(P) : DH;` is a constant expression in the class instantiations
+__device__ __forceinline__ int pad_dh(const AttnParamsPad& P) { return P.dh; }
+__device__ __forceinline__ int pad_dh(const AttnParams&) { return 0; }
 
 // Block -> (sequence, head, query block).  Workgroups are dealt to the 8 XCDs round-robin by linear id, so XCD x gets
 // the logical range [x * chunk, (x + 1) * chunk): all heads and query blocks of a sequence run on one XCD at about the
@@ -120,11 +136,12 @@ __device__ __forceinline__ bool block_coords(const AttnParams& P, int& seq, int&
 }
 
 // out[tok0 .. tok0+n)[head h] = 0 (sequences without keys)
-template <int DH>
-__device__ __forceinline__ void zero_rows(const AttnParams& P, int tok0, int n, int h) {
-    constexpr int CPR = DH / 4;                       // 8-byte pieces (the output is only 8-byte aligned)
+template <int DH, bool PAD = false>
+__device__ __forceinline__ void zero_rows(const AttnArgs<PAD>& P, int tok0, int n, int h) {
+    const int dh = PAD ? pad_dh(P) : DH;
+    const int CPR = dh / 4;                           // 8-byte pieces (the output is only 8-byte aligned)
     for (int i = threadIdx.x; i < n * CPR; i += blockDim.x)
-        *reinterpret_cast<u32x2_t*>(P.out + (int64_t)(tok0 + i / CPR) * P.o_stride + h * DH + (i % CPR) * 4) =
+        *reinterpret_cast<u32x2_t*>(P.out + (int64_t)(tok0 + i / CPR) * P.o_stride + h * dh + (i % CPR) * 4) =
             (u32x2_t){0u, 0u};
 }
 
@@ -350,9 +367,11 @@ __device__ __forceinline__ void attn_tile_short(int rem, const char* sK, const c
 
 // (2 query groups with ALiBi sit at the 170-register edge of three waves per SIMD -- the CRE stream's self attention; the
 // integer-maximum form compiles to 172 without the bound)
-template <int DH, int QG, bool ALIBI, int DT = VF_BF16, int DBG = 0, bool QL = false>
-__global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) void attn_fwd_kernel(AttnParams P) {
+// PAD: a head dim below the class DH (AttnParamsPad::dh, see the file header); classes 192 / 256 exist only in this form.
+template <int DH, int QG, bool ALIBI, int DT = VF_BF16, int DBG = 0, bool QL = false, bool PAD = false>
+__global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) void attn_fwd_kernel(AttnArgs<PAD> P) {
     using frag_t = typename Op16<DT>::frag;
+    const int dh = PAD ? pad_dh(P) : DH;               // true head dim: chunks [dh / 8, CPR) of a row are zeros in LDS
     constexpr int CPR = DH / 8;                       // 16-byte chunks per K/V row
     constexpr int NCHUNK = BKV * CPR;                 // chunks per tile
     constexpr int NLD = (NCHUNK + 255) / 256;         // chunk loads per thread per operand
@@ -371,7 +390,7 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
     const int qb0 = qblk * BQ;
     if (qb0 >= len_q) return;                         // block-uniform
     if (len_k <= 0) {                                 // no keys: the output rows are zeros (flash-attn convention)
-        zero_rows<DH>(P, q_tok0 + qb0, (len_q - qb0) < BQ ? (len_q - qb0) : BQ, h);
+        zero_rows<DH, PAD>(P, q_tok0 + qb0, (len_q - qb0) < BQ ? (len_q - qb0) : BQ, h);
         return;
     }
 
@@ -398,12 +417,12 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
     for (int qg = 0; qg < QG; ++qg) {
         q_abs[qg] = qb0 + (wave * QG + qg) * 16 + r;
         const int row = q_abs[qg] < len_q ? q_abs[qg] : len_q - 1;
-        const unsigned short* qp = P.q + (int64_t)(q_tok0 + row) * P.q_stride + h * DH;
+        const unsigned short* qp = P.q + (int64_t)(q_tok0 + row) * P.q_stride + h * dh;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int d0 = 32 * ks + 8 * g;
             u32x4_t raw = q_pad_chunk<DT>(d0, DH);
-            if (d0 < DH) raw = *reinterpret_cast<const u32x4_t*>(qp + d0);
+            if (d0 < dh) raw = *reinterpret_cast<const u32x4_t*>(qp + d0);
             qf[qg][ks] = *reinterpret_cast<frag_t*>(&raw);
         }
     }
@@ -433,8 +452,8 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
     constexpr int NLD2 = 2 * NCHUNK / 256;
     static_assert(2 * NCHUNK % 256 == 0, "staging items must divide over the threads");
     u32x4_t kvreg[NLD2];
-    const unsigned short* kbase = P.k + (int64_t)k_tok0 * P.k_stride + h * DH;
-    const unsigned short* vbase = P.v + (int64_t)k_tok0 * P.v_stride + h * DH;
+    const unsigned short* kbase = P.k + (int64_t)k_tok0 * P.k_stride + h * dh;
+    const unsigned short* vbase = P.v + (int64_t)k_tok0 * P.v_stride + h * dh;
     // per-item constants of the staging list: source pointer at key 0 of the sequence and the row stride; the per-tile
     // address is base + min(key, len_k - 1) * stride with a 24-bit multiply (full rate; max_seqlen_k * stride < 2^31 is
     // checked at launch) -- the 64-bit multiply this replaces cost three quarter-rate VALU instructions per load
@@ -449,6 +468,11 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
         kv_row[i] = ci / CPR;
         kv_src[i] = (is_v ? vbase : kbase) + (ci % CPR) * 8;
         kv_stride[i] = (unsigned)(is_v ? P.v_stride : P.k_stride);
+        // PAD: a chunk past the head (c >= dh / 8) re-reads the head's last chunk -- in bounds, no branch around the
+        // prefetch -- and write_lds stores zeros in its place
+        if constexpr (PAD) {
+            if (ci % CPR >= dh / 8) kv_src[i] = (is_v ? vbase : kbase) + (dh / 8 - 1) * 8;
+        }
     }
     auto load_regs = [&](int t) {
 #pragma unroll
@@ -469,7 +493,7 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
             const int row = ci / CPR, c = ci % CPR;
             const int off = is_v ? K_TILE_BYTES + row * VROW + (c << 4)
                                  : row * K_ROW_BYTES + ((c ^ KLayout<DH>::swz(row)) << 4);
-            *reinterpret_cast<u32x4_t*>(sK + off) = kvreg[i];
+            *reinterpret_cast<u32x4_t*>(sK + off) = (PAD && c >= dh / 8) ? (u32x4_t){0u, 0u, 0u, 0u} : kvreg[i];
         }
         if (HwMask<DH>::value && tid < BKV)          // pad slot d = DH of every key row: 0 or the mask value
             *reinterpret_cast<u32x4_t*>(sK + tid * K_ROW_BYTES + ((CPR ^ ((tid >> 1) & 7)) << 4)) =
@@ -518,13 +542,13 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
         const float l = l_acc[qg][0];
         const float inv = 1.0f / l;
         if (q_abs[qg] < len_q) {
-            unsigned short* op = P.out + (int64_t)(q_tok0 + q_abs[qg]) * P.o_stride + h * DH + 4 * g;
+            unsigned short* op = P.out + (int64_t)(q_tok0 + q_abs[qg]) * P.o_stride + h * dh + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
                 u32x2_t pk;
                 pk[0] = Op16<DT>::pack2(o[qg][dt][0] * inv, o[qg][dt][1] * inv);
                 pk[1] = Op16<DT>::pack2(o[qg][dt][2] * inv, o[qg][dt][3] * inv);
-                *reinterpret_cast<u32x2_t*>(op + 16 * dt) = pk;
+                if (!PAD || 16 * dt + 4 * g < dh) *reinterpret_cast<u32x2_t*>(op + 16 * dt) = pk;   // 4 columns: all < dh or none
             }
         }
     }
@@ -561,10 +585,12 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
 #ifndef VF_X32_WIDE_STORE
 #define VF_X32_WIDE_STORE 1
 #endif
-template <int DT, int QB, bool FAST = false>
-__global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
+// PAD: a head dim of 8 ... 40 in the 48 class (AttnParamsPad::dh): columns [dh, 48) of Q, K and V are zeros
+template <int DT, int QB, bool FAST = false, bool PAD = false>
+__global__ __launch_bounds__(256) void attn_x32_kernel(AttnArgs<PAD> P) {
     using frag_t = typename Op16<DT>::frag;
     constexpr int DH = 48, KSTEPS = 3, KROW = 112, VROW = 192;
+    const int dh = PAD ? pad_dh(P) : DH;
     constexpr int K_TILE = BKV * KROW, V_TILE = BKV * VROW, STAGE = K_TILE + V_TILE;
     constexpr int CPR = DH / 8, NCHUNK = BKV * CPR, NLD2 = 2 * NCHUNK / 256;
     constexpr int BQ = 4 * QB * 32;
@@ -578,7 +604,7 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
     const int qb0 = qblk * BQ;
     if (qb0 >= len_q) return;                         // block-uniform
     if (len_k <= 0) {
-        zero_rows<DH>(P, q_tok0 + qb0, (len_q - qb0) < BQ ? (len_q - qb0) : BQ, hd);
+        zero_rows<DH, PAD>(P, q_tok0 + qb0, (len_q - qb0) < BQ ? (len_q - qb0) : BQ, hd);
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -598,10 +624,11 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
     for (int qb = 0; qb < QB; ++qb) {
         q_abs[qb] = qb0 + (wave * QB + qb) * 32 + ql;
         const int row = q_abs[qb] < len_q ? q_abs[qb] : len_q - 1;
-        const unsigned short* qp = P.q + (int64_t)(q_tok0 + row) * P.q_stride + hd * DH + 8 * h;
+        const unsigned short* qp = P.q + (int64_t)(q_tok0 + row) * P.q_stride + hd * dh + 8 * h;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) {
-            const u32x4_t raw = *reinterpret_cast<const u32x4_t*>(qp + 16 * ks);
+            u32x4_t raw = (u32x4_t){0u, 0u, 0u, 0u};
+            if (!PAD || 16 * ks + 8 * h < dh) raw = *reinterpret_cast<const u32x4_t*>(qp + 16 * ks);
             qf[qb][ks] = __builtin_bit_cast(frag_t, raw);
         }
     }
@@ -620,18 +647,20 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
     // ---- K/V tile staging: global -> registers -> LDS, one list of 2 * NCHUNK 16-byte items, NLD2 per thread (see
     // attn_fwd_kernel: no divergent branch around the prefetch)
     u32x4_t kvreg[NLD2];
-    const unsigned short* kbase = P.k + (int64_t)k_tok0 * P.k_stride + hd * DH;
-    const unsigned short* vbase = P.v + (int64_t)k_tok0 * P.v_stride + hd * DH;
+    const unsigned short* kbase = P.k + (int64_t)k_tok0 * P.k_stride + hd * dh;
+    const unsigned short* vbase = P.v + (int64_t)k_tok0 * P.v_stride + hd * dh;
     const unsigned short* kv_src[NLD2];
     unsigned kv_stride[NLD2];
     int kv_row[NLD2], kv_off[NLD2];
+    bool kv_pad[NLD2];                                // PAD: the item is a chunk past the head (loads in bounds, stores zeros)
 #pragma unroll
     for (int i = 0; i < NLD2; ++i) {
         const int item = tid + 256 * i;
         const bool is_v = item >= NCHUNK;
         const int ci = is_v ? item - NCHUNK : item;
         kv_row[i] = ci / CPR;
-        kv_src[i] = (is_v ? vbase : kbase) + (ci % CPR) * 8;
+        kv_pad[i] = PAD && ci % CPR >= dh / 8;
+        kv_src[i] = (is_v ? vbase : kbase) + (kv_pad[i] ? dh / 8 - 1 : ci % CPR) * 8;
         kv_stride[i] = (unsigned)(is_v ? P.v_stride : P.k_stride);
         kv_off[i] = is_v ? K_TILE + kv_row[i] * VROW + (ci % CPR) * 16 : kv_row[i] * KROW + (ci % CPR) * 16;
     }
@@ -645,7 +674,8 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
     };
     auto write_lds = [&](int stage) {
 #pragma unroll
-        for (int i = 0; i < NLD2; ++i) *reinterpret_cast<u32x4_t*>(smem + stage * STAGE + kv_off[i]) = kvreg[i];
+        for (int i = 0; i < NLD2; ++i)
+            *reinterpret_cast<u32x4_t*>(smem + stage * STAGE + kv_off[i]) = kv_pad[i] ? (u32x4_t){0u, 0u, 0u, 0u} : kvreg[i];
     };
 
     // fragment addresses inside a stage
@@ -820,7 +850,7 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
         const float inv = 1.0f / __uint_as_float(sw[0]);              // the lower half's value in both halves
         if (wide || q_abs[qb] < len_q) {
             unsigned short* op = wide ? reinterpret_cast<unsigned short*>(oreg + (qb * 32 + ql) * OPITCH) + 4 * h
-                                      : P.out + (int64_t)(q_tok0 + q_abs[qb]) * P.o_stride + hd * DH + 4 * h;
+                                      : P.out + (int64_t)(q_tok0 + q_abs[qb]) * P.o_stride + hd * dh + 4 * h;
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -828,7 +858,7 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
                     u32x2_t pk;
                     pk[0] = Op16<DT>::pack2(o[qb][dt][4 * gq] * inv, o[qb][dt][4 * gq + 1] * inv);
                     pk[1] = Op16<DT>::pack2(o[qb][dt][4 * gq + 2] * inv, o[qb][dt][4 * gq + 3] * inv);
-                    *reinterpret_cast<u32x2_t*>(op + 32 * dt + 8 * gq) = pk;
+                    if (!PAD || wide || 32 * dt + 8 * gq + 4 * h < dh) *reinterpret_cast<u32x2_t*>(op + 32 * dt + 8 * gq) = pk;
                 }
         }
     }
@@ -844,8 +874,8 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
             const int item = lane + 64 * i, row = item / (DH / 8), cc = item - row * (DH / 8);
-            if (item < NCH && q_w0 + row < len_q)
-                *reinterpret_cast<u32x4_t*>(P.out + (int64_t)(q_tok0 + q_w0 + row) * P.o_stride + hd * DH + cc * 8) = v[i];
+            if (item < NCH && q_w0 + row < len_q && (!PAD || cc < dh / 8))
+                *reinterpret_cast<u32x4_t*>(P.out + (int64_t)(q_tok0 + q_w0 + row) * P.o_stride + hd * dh + cc * 8) = v[i];
         }
     }
 }
@@ -863,10 +893,12 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnParams P) {
 // tiled kernels, which serve the same queries in other batch geometries.  (The no-maximum form of attn_x32_kernel was
 // measured here too: -2 % on the gene stream's self attention -- this kernel waits for its loads, not for its exponentials --
 // and it cannot be bit-identical to mode 2, whose s - m rounds; not kept.)
-template <int DH, int QG, bool ALIBI, int DT = VF_BF16, bool QL = false>
-__global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(AttnParams P, int k_rows) {
+// PAD: a head dim below the class DH (AttnParamsPad::dh): chunks [dh / 8, CPR) are staged as zeros
+template <int DH, int QG, bool ALIBI, int DT = VF_BF16, bool QL = false, bool PAD = false>
+__global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(AttnArgs<PAD> P, int k_rows) {
     constexpr int SM = QL ? 2 : 0;
     using frag_t = typename Op16<DT>::frag;
+    const int dh = PAD ? pad_dh(P) : DH;
     constexpr int CPR = DH / 8;
     constexpr int NDT = DH / 16;
     constexpr int VROW = VLayout<DH>::ROW;
@@ -883,7 +915,7 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
     const int k_tok0 = P.cu_k[seq], len_k = P.cu_k[seq + 1] - k_tok0;
     if (len_q <= 0) return;
     if (len_k <= 0) {
-        zero_rows<DH>(P, q_tok0, len_q, h);
+        zero_rows<DH, PAD>(P, q_tok0, len_q, h);
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -905,19 +937,19 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
     for (int qg = 0; qg < QG; ++qg) {
         q_abs[qg] = (wave + 4 * qg) * 16 + r;
         const int row = q_abs[qg] < len_q ? q_abs[qg] : len_q - 1;
-        const unsigned short* qp = P.q + (int64_t)(q_tok0 + row) * P.q_stride + h * DH;
+        const unsigned short* qp = P.q + (int64_t)(q_tok0 + row) * P.q_stride + h * dh;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int d0 = 32 * ks + 8 * g;
             u32x4_t raw = q_pad_chunk<DT>(d0, DH);
-            if (d0 < DH) raw = *reinterpret_cast<const u32x4_t*>(qp + d0);
+            if (d0 < dh) raw = *reinterpret_cast<const u32x4_t*>(qp + d0);
             qf[qg][ks] = *reinterpret_cast<frag_t*>(&raw);
         }
         q_pos[qg] = (float)(q_abs[qg] + (P.q_at_start ? 0 : len_k - len_q));
     }
     // ---- stage K (swizzled, zero pad chunks) and V; rows >= len_k replicate the last key (finite, masked later)
-    const unsigned short* kbase = P.k + (int64_t)k_tok0 * P.k_stride + h * DH;
-    const unsigned short* vbase = P.v + (int64_t)k_tok0 * P.v_stride + h * DH;
+    const unsigned short* kbase = P.k + (int64_t)k_tok0 * P.k_stride + h * dh;
+    const unsigned short* vbase = P.v + (int64_t)k_tok0 * P.v_stride + h * dh;
     {
         u32x4_t kbuf[MAXIT], vbuf[MAXIT];
 #pragma unroll
@@ -926,7 +958,7 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
             const int row = ci >> 3, cc = ci & 7;
             kbuf[it] = (HwMask<DH>::value && cc == CPR) ? mask_chunk<DT>(row < len_k) : (u32x4_t){0u, 0u, 0u, 0u};
             vbuf[it] = (u32x4_t){0u, 0u, 0u, 0u};
-            if (ci < nchunks && cc < CPR) {
+            if (ci < nchunks && cc < dh / 8) {
                 const int key = row < len_k ? row : len_k - 1;
                 kbuf[it] = *reinterpret_cast<const u32x4_t*>(kbase + (int64_t)key * P.k_stride + cc * 8);
                 vbuf[it] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)key * P.v_stride + cc * 8);
@@ -1000,13 +1032,13 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
         const float l = l_acc[qg][0];
         const float inv = 1.0f / l;
         if (q_abs[qg] < len_q) {
-            unsigned short* op = P.out + (int64_t)(q_tok0 + q_abs[qg]) * P.o_stride + h * DH + 4 * g;
+            unsigned short* op = P.out + (int64_t)(q_tok0 + q_abs[qg]) * P.o_stride + h * dh + 4 * g;
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
                 u32x2_t pk;
                 pk[0] = Op16<DT>::pack2(o[qg][dt][0] * inv, o[qg][dt][1] * inv);
                 pk[1] = Op16<DT>::pack2(o[qg][dt][2] * inv, o[qg][dt][3] * inv);
-                *reinterpret_cast<u32x2_t*>(op + 16 * dt) = pk;
+                if (!PAD || 16 * dt + 4 * g < dh) *reinterpret_cast<u32x2_t*>(op + 16 * dt) = pk;
             }
         }
     }
@@ -1036,10 +1068,13 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
 // budget stays that of three waves per SIMD: at (256, 2) the compiler hoists loads up to 256 VGPRs + 47 spilled and the launch
 // takes 2369 us instead of 1329 us (168 VGPRs, 12 spilled) -- profiles/r04_k.
 // ROWS: Q / K / V rows are fetched through AttnParams::q_rows / kv_rows (one index load per row in front of the data loads).
-template <int DH, bool ALIBI, int DT = VF_BF16, bool QL = false, int NPASS = 2, bool ROWS = false>
-__global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnParams P, int k_rows) {
+// PAD: a head dim below the class DH (AttnParamsPad::dh; no row-map form)
+template <int DH, bool ALIBI, int DT = VF_BF16, bool QL = false, int NPASS = 2, bool ROWS = false, bool PAD = false>
+__global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnArgs<PAD> P, int k_rows) {
+    static_assert(!(ROWS && PAD), "padded head dims have no row-map form");
     constexpr int SM = QL ? 2 : 0;
     using frag_t = typename Op16<DT>::frag;
+    const int dh = PAD ? pad_dh(P) : DH;
     constexpr int CPR = DH / 8, NDT = DH / 16, QG = 2;
     constexpr int VROW = VLayout<DH>::ROW;
     constexpr int K_ROW_BYTES = KLayout<DH>::ROW, KS = KLayout<DH>::KS;
@@ -1055,7 +1090,7 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnParams P, int k
     const int k_tok0 = P.cu_k[seq], len_k = P.cu_k[seq + 1] - k_tok0;
     if (len_q <= 0) return;
     if (len_k <= 0) {
-        zero_rows<DH>(P, q_tok0, len_q, h);
+        zero_rows<DH, PAD>(P, q_tok0, len_q, h);
         return;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1075,18 +1110,18 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnParams P, int k
             const int qa = (wave + 4 * (QG * ps + qg)) * 16 + r;
             const int row = qa < len_q ? qa : len_q - 1;
             const int64_t qrow = (ROWS && P.q_rows) ? P.q_rows[q_tok0 + row] : (int64_t)(q_tok0 + row);
-            const unsigned short* qp = P.q + qrow * P.q_stride + h * DH;
+            const unsigned short* qp = P.q + qrow * P.q_stride + h * dh;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const int d0 = 32 * ks + 8 * g;
                 u32x4_t raw = q_pad_chunk<DT>(d0, DH);
-                if (d0 < DH) raw = *reinterpret_cast<const u32x4_t*>(qp + d0);
+                if (d0 < dh) raw = *reinterpret_cast<const u32x4_t*>(qp + d0);
                 qf[ps][qg][ks] = *reinterpret_cast<frag_t*>(&raw);
             }
         }
     // ---- stage K (swizzled, zero pad chunks) and V; rows >= len_k replicate the last key (finite, masked later)
-    const unsigned short* kbase = P.k + h * DH;
-    const unsigned short* vbase = P.v + h * DH;
+    const unsigned short* kbase = P.k + h * dh;
+    const unsigned short* vbase = P.v + h * dh;
     {
         u32x4_t kbuf[MAXIT], vbuf[MAXIT];
         int64_t src[MAXIT];                          // source row of every staged row: all index loads in flight before the data loads
@@ -1102,7 +1137,7 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnParams P, int k
             const int row = ci >> 3, cc = ci & 7;
             kbuf[it] = (HwMask<DH>::value && cc == CPR) ? mask_chunk<DT>(row < len_k) : (u32x4_t){0u, 0u, 0u, 0u};
             vbuf[it] = (u32x4_t){0u, 0u, 0u, 0u};
-            if (row < rows_v && cc < CPR) {
+            if (row < rows_v && cc < dh / 8) {
                 if (row < rows_k) kbuf[it] = *reinterpret_cast<const u32x4_t*>(kbase + src[it] * P.k_stride + cc * 8);
                 vbuf[it] = *reinterpret_cast<const u32x4_t*>(vbase + src[it] * P.v_stride + cc * 8);
             }
@@ -1168,13 +1203,13 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnParams P, int k
         for (int qg = 0; qg < QG; ++qg) {
             const float inv = 1.0f / l_acc[qg][0];
             if (q_abs[qg] < len_q) {
-                unsigned short* op = P.out + (int64_t)(q_tok0 + q_abs[qg]) * P.o_stride + h * DH + 4 * g;
+                unsigned short* op = P.out + (int64_t)(q_tok0 + q_abs[qg]) * P.o_stride + h * dh + 4 * g;
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     u32x2_t pk;
                     pk[0] = Op16<DT>::pack2(o[qg][dt][0] * inv, o[qg][dt][1] * inv);
                     pk[1] = Op16<DT>::pack2(o[qg][dt][2] * inv, o[qg][dt][3] * inv);
-                    *reinterpret_cast<u32x2_t*>(op + 16 * dt) = pk;
+                    if (!PAD || 16 * dt + 4 * g < dh) *reinterpret_cast<u32x2_t*>(op + 16 * dt) = pk;
                 }
             }
         }
@@ -1206,11 +1241,11 @@ static unsigned set_grid(AttnParams& P, int n_seq, int nqb) {
 // dynamic LDS of the tiled kernel: two (K tile + V tile) stages
 template <int DH> constexpr int attn_fwd_lds() { return 2 * (KLayout<DH>::TILE + VLayout<DH>::TILE); }
 
-template <int DH, int QG, bool ALIBI, int DT, int DBG, bool QL>
-int launch_fwd_k(const AttnParams& P, dim3 grid, hipStream_t st) {
-    auto kern = attn_fwd_kernel<DH, QG, ALIBI, DT, DBG, QL>;
+template <int DH, int QG, bool ALIBI, int DT, int DBG, bool QL, bool PAD>
+int launch_fwd_k(const AttnParamsPad& P, dim3 grid, hipStream_t st) {
+    auto kern = attn_fwd_kernel<DH, QG, ALIBI, DT, DBG, QL, PAD>;
     constexpr int lds = attn_fwd_lds<DH>();
-    if (lds > 65536) {                             // dh = 128 only: above the default dynamic-LDS limit
+    if (lds > 65536) {                             // dh >= 128: above the default dynamic-LDS limit (dh 256: 132 KiB)
         static bool attr_set[VF_MAX_DEVICES] = {};
         const int dev = vf_current_device();
         if (dev < 0 || !attr_set[dev]) {
@@ -1224,24 +1259,24 @@ int launch_fwd_k(const AttnParams& P, dim3 grid, hipStream_t st) {
         }
     }
     vf_note_kernel(1, QG == 1 ? "attn_fwd_kernel<64-query blocks>" : QG == 2 ? "attn_fwd_kernel<128-query blocks>" : "attn_fwd_kernel<256-query blocks>");
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, P);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, static_cast<const AttnArgs<PAD>&>(P));
     VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
     return VF_OK;
 }
 
 // q carrying the softmax scale (AttnParams::q_log2) selects the integer-maximum instantiation (attn_tile mode 2)
-template <int DH, int QG, bool ALIBI, int DT, int DBG = 0>
-int launch_fwd(const AttnParams& P, dim3 grid, hipStream_t st) {
+template <int DH, int QG, bool ALIBI, int DT, int DBG = 0, bool PAD = false>
+int launch_fwd(const AttnParamsPad& P, dim3 grid, hipStream_t st) {
     if (const int rc = no_row_map(P, "attn_fwd_kernel")) return rc;
-    if (DBG == 0 && P.q_log2) return launch_fwd_k<DH, QG, ALIBI, DT, 0, true>(P, grid, st);
-    return launch_fwd_k<DH, QG, ALIBI, DT, DBG, false>(P, grid, st);
+    if (DBG == 0 && P.q_log2) return launch_fwd_k<DH, QG, ALIBI, DT, 0, true, PAD>(P, grid, st);
+    return launch_fwd_k<DH, QG, ALIBI, DT, DBG, false, PAD>(P, grid, st);
 }
 
-template <int DH, int QG, bool ALIBI, int DT, bool QL>
-int launch_short_k(AttnParams P, int n_seq, int max_k, hipStream_t st) {
+template <int DH, int QG, bool ALIBI, int DT, bool QL, bool PAD>
+int launch_short_k(AttnParamsPad P, int n_seq, int max_k, hipStream_t st) {
     const int k_rows = ((max_k + BKV - 1) / BKV) * BKV;
     const int lds = k_rows * (KLayout<DH>::ROW + VLayout<DH>::ROW);
-    auto kern = attn_short_kernel<DH, QG, ALIBI, DT, QL>;
+    auto kern = attn_short_kernel<DH, QG, ALIBI, DT, QL, PAD>;
     static bool attr_set[VF_MAX_DEVICES] = {};    // the attribute is per device (and per instantiation)
     const int dev = vf_current_device();
     if (dev < 0 || !attr_set[dev]) {
@@ -1255,7 +1290,7 @@ int launch_short_k(AttnParams P, int n_seq, int max_k, hipStream_t st) {
     }
     const unsigned nblk = set_grid(P, n_seq, 1);
     vf_note_kernel(1, "attn_short_kernel");
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, P, k_rows);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, static_cast<const AttnArgs<PAD>&>(P), k_rows);
     VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
     return VF_OK;
 }
@@ -1267,12 +1302,12 @@ static inline void short2_rows(int max_k, int& kr, int& vr) {
     vr = tl * BKV + (rem <= 32 ? 32 : BKV);
 }
 
-template <int DH, bool ALIBI, int DT, bool QL, int NPASS, bool ROWS = false>
-int launch_short2_k(AttnParams P, int n_seq, int max_k, hipStream_t st) {
+template <int DH, bool ALIBI, int DT, bool QL, int NPASS, bool ROWS = false, bool PAD = false>
+int launch_short2_k(AttnParamsPad P, int n_seq, int max_k, hipStream_t st) {
     int kr, vr;
     short2_rows(max_k, kr, vr);
     const int lds = kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW;
-    auto kern = attn_short2_kernel<DH, ALIBI, DT, QL, NPASS, ROWS>;
+    auto kern = attn_short2_kernel<DH, ALIBI, DT, QL, NPASS, ROWS, PAD>;
     static bool attr_set[VF_MAX_DEVICES] = {};
     const int dev = vf_current_device();
     if (dev < 0 || !attr_set[dev]) {
@@ -1291,44 +1326,45 @@ int launch_short2_k(AttnParams P, int n_seq, int max_k, hipStream_t st) {
     P.dbg = vf_tuning_env("VF_ATTN_SHORT_DBG", 0);
     const int lds_probe = vf_tuning_env("VF_ATTN_SHORT_LDS", 0);     // occupancy probe: request this many bytes instead (>= lds)
     if (lds_probe > lds) {
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds_probe, st, P, kr);
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds_probe, st, static_cast<const AttnArgs<PAD>&>(P), kr);
         VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
         return VF_OK;
     }
 #endif
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, P, kr);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, static_cast<const AttnArgs<PAD>&>(P), kr);
     VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
     return VF_OK;
 }
 
-template <int DH, bool ALIBI, int DT, int NPASS = 2>
-int launch_short2(AttnParams P, int n_seq, int max_k, hipStream_t st) {
+template <int DH, bool ALIBI, int DT, int NPASS = 2, bool PAD = false>
+int launch_short2(AttnParamsPad P, int n_seq, int max_k, hipStream_t st) {
     if (P.q_rows || P.kv_rows) {                 // only the model's call form (pre-scaled q) has a row-map instantiation
-        if constexpr ((DH == 64 && !ALIBI) || (DH == 48 && ALIBI && NPASS == 2)) {
+        if constexpr (!PAD && ((DH == 64 && !ALIBI) || (DH == 48 && ALIBI && NPASS == 2))) {
             if (P.q_log2) return launch_short2_k<DH, ALIBI, DT, true, NPASS, true>(P, n_seq, max_k, st);
         }
         vf_set_error("vf_attn_varlen_fwd_rows: no row-map kernel for this geometry (ask vf_attn_rows_supported first)");
         return VF_ERR_INVALID_ARG;
     }
-    if (P.q_log2) return launch_short2_k<DH, ALIBI, DT, true, NPASS>(P, n_seq, max_k, st);
-    return launch_short2_k<DH, ALIBI, DT, false, NPASS>(P, n_seq, max_k, st);
+    if (P.q_log2) return launch_short2_k<DH, ALIBI, DT, true, NPASS, false, PAD>(P, n_seq, max_k, st);
+    return launch_short2_k<DH, ALIBI, DT, false, NPASS, false, PAD>(P, n_seq, max_k, st);
 }
 
-template <int DH, int QG, bool ALIBI, int DT>
-int launch_short(AttnParams P, int n_seq, int max_k, hipStream_t st) {
+template <int DH, int QG, bool ALIBI, int DT, bool PAD = false>
+int launch_short(AttnParamsPad P, int n_seq, int max_k, hipStream_t st) {
     if (const int rc = no_row_map(P, "attn_short_kernel")) return rc;
-    if (P.q_log2) return launch_short_k<DH, QG, ALIBI, DT, true>(P, n_seq, max_k, st);
-    return launch_short_k<DH, QG, ALIBI, DT, false>(P, n_seq, max_k, st);
+    if (P.q_log2) return launch_short_k<DH, QG, ALIBI, DT, true, PAD>(P, n_seq, max_k, st);
+    return launch_short_k<DH, QG, ALIBI, DT, false, PAD>(P, n_seq, max_k, st);
 }
 
-template <int DT, int QB>
-int launch_x32(const AttnParams& P, dim3 grid, hipStream_t st) {
+template <int DT, int QB, bool PAD = false>
+int launch_x32(const AttnParamsPad& P, dim3 grid, hipStream_t st) {
     if (const int rc = no_row_map(P, "attn_x32_kernel")) return rc;
     constexpr int lds = 2 * BKV * (112 + 192);
     static const int nomax = vf_tuning_env("VF_ATTN_NOMAX", 1);    // 0: running maximum always (A/B)
     vf_note_kernel(1, QB == 2 ? "attn_x32_kernel<64 queries per wave>" : "attn_x32_kernel<32 queries per wave>");
-    if (P.q_log2 && nomax) hipLaunchKernelGGL((attn_x32_kernel<DT, QB, true>), grid, dim3(256), lds, st, P);
-    else hipLaunchKernelGGL((attn_x32_kernel<DT, QB, false>), grid, dim3(256), lds, st, P);
+    const AttnArgs<PAD>& A = P;
+    if (P.q_log2 && nomax) hipLaunchKernelGGL((attn_x32_kernel<DT, QB, true, PAD>), grid, dim3(256), lds, st, A);
+    else hipLaunchKernelGGL((attn_x32_kernel<DT, QB, false, PAD>), grid, dim3(256), lds, st, A);
     VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
     return VF_OK;
 }
@@ -1374,12 +1410,16 @@ static bool rows_supported(int dh, bool alibi, long n_seq, int H, int max_q, int
     return false;
 }
 
-template <int DH, bool ALIBI, int DT>
-int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
-    if ((P.q_rows || P.kv_rows) && !rows_supported(DH, ALIBI, n_seq, P.H, max_q, max_k, P.q_log2 != 0)) {
+// PAD: DH is the class of the true head dim P.dh (vf_attn_varlen_fwd_v3).  The routing below is the class's, unchanged, so a
+// padded head dim reaches the same kernel with the same block shape as a class-dh call of the same geometry.  The row-map
+// check keys on the TRUE head dim (rows_supported has no padded entries, as vf_attn_rows_supported reports).
+template <int DH, bool ALIBI, int DT, bool PAD = false>
+int launch_attn(AttnParamsPad P, int n_seq, int max_q, int max_k, hipStream_t st) {
+    const int dh = PAD ? P.dh : DH;
+    if ((P.q_rows || P.kv_rows) && !rows_supported(dh, ALIBI, n_seq, P.H, max_q, max_k, P.q_log2 != 0)) {
         vf_set_error("vf_attn_varlen_fwd_rows: no row-map kernel for dh=%d alibi=%d n_seq=%d H=%d max_q=%d max_k=%d "
                      "(vf_attn_rows_supported says which geometries have one; gather the rows first otherwise)",
-                     DH, (int)ALIBI, n_seq, P.H, max_q, max_k);
+                     dh, (int)ALIBI, n_seq, P.H, max_q, max_k);
         return VF_ERR_INVALID_ARG;
     }
     // Measured on MI355X (scripts/attn_bench.py, 8 genes): the one-block-per-(sequence, head) kernel wins for the gene
@@ -1393,15 +1433,17 @@ int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
     if constexpr (DH == 48 && !ALIBI) {
         const int x32 = vf_tuning_env("VF_ATTN_X32", 1);             // 0: the 16x16x32 kernels (A/B; read per launch in the tuning library)
         if (x32) {
-#ifdef VF_TUNING   // VF_ATTN_X32PP=1: the anti-phase experiment (attn_x32pp_kernel: slower, see its header)
-            static const int pp = vf_tuning_env("VF_ATTN_X32PP", 0);
-            static const int nomax = vf_tuning_env("VF_ATTN_NOMAX", 1);
-            if (pp != 0 && nomax != 0 && x32 != 2 && P.q_log2 && (long)n_seq * P.H * ((max_q + 511) / 512) >= 1024)
-                return launch_x32pp<DT>(P, dim3(set_grid(P, n_seq, (max_q + 511) / 512)), st);
+#ifdef VF_TUNING   // VF_ATTN_X32PP=1: the anti-phase experiment (attn_x32pp_kernel: slower, see its header; class dh only)
+            if constexpr (!PAD) {
+                static const int pp = vf_tuning_env("VF_ATTN_X32PP", 0);
+                static const int nomax = vf_tuning_env("VF_ATTN_NOMAX", 1);
+                if (pp != 0 && nomax != 0 && x32 != 2 && P.q_log2 && (long)n_seq * P.H * ((max_q + 511) / 512) >= 1024)
+                    return launch_x32pp<DT>(P, dim3(set_grid(P, n_seq, (max_q + 511) / 512)), st);
+            }
 #endif
             if (x32 != 2 && (long)n_seq * P.H * ((max_q + 255) / 256) >= 2048)
-                return launch_x32<DT, 2>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
-            return launch_x32<DT, 1>(P, dim3(set_grid(P, n_seq, (max_q + 127) / 128)), st);
+                return launch_x32<DT, 2, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
+            return launch_x32<DT, 1, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 127) / 128)), st);
         }
     }
     if constexpr (DH <= 48) {
@@ -1412,9 +1454,9 @@ int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
             int kr, vr;
             short2_rows(max_k, kr, vr);
             if (short2 && 3 * (kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW) <= 160 * 1024)
-                return launch_short2<DH, ALIBI, DT>(P, n_seq, max_k, st);
-            if (max_q <= 192) return launch_short<DH, 3, ALIBI, DT>(P, n_seq, max_k, st);
-            return launch_short<DH, 4, ALIBI, DT>(P, n_seq, max_k, st);
+                return launch_short2<DH, ALIBI, DT, 2, PAD>(P, n_seq, max_k, st);
+            if (max_q <= 192) return launch_short<DH, 3, ALIBI, DT, PAD>(P, n_seq, max_k, st);
+            return launch_short<DH, 4, ALIBI, DT, PAD>(P, n_seq, max_k, st);
         }
     }
     if constexpr (DH == 64 || DH == 32) {
@@ -1427,7 +1469,7 @@ int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
             int kr, vr;
             short2_rows(max_k, kr, vr);
             if (3 * (kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW) <= 160 * 1024)
-                return launch_short2<DH, ALIBI, DT, 1>(P, n_seq, max_k, st);
+                return launch_short2<DH, ALIBI, DT, 1, PAD>(P, n_seq, max_k, st);
         }
         // 129-256-token chunks (seq2reg's 200-token gene chunks): the same kernel in its two-pass form, one block per (chunk,
         // head) with a 62 KB image (two resident blocks per CU) instead of four 64-query blocks of the tiled kernel that each
@@ -1436,7 +1478,7 @@ int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
             int kr, vr;
             short2_rows(max_k, kr, vr);
             if (2 * (kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW) <= 160 * 1024)
-                return launch_short2<DH, ALIBI, DT, 2>(P, n_seq, max_k, st);
+                return launch_short2<DH, ALIBI, DT, 2, PAD>(P, n_seq, max_k, st);
         }
     }
     // long query streams: 2 query groups per wave (halves K/V LDS traffic per MFMA; for seq2reg windows, 70-200 queries,
@@ -1449,7 +1491,7 @@ int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
         if (max_q > 256 && (long)n_seq * P.H * ((max_q + 127) / 128) >= 1024) {
             const dim3 grid(set_grid(P, n_seq, (max_q + 127) / 128));
 #ifdef VF_TUNING                                   // libvf_hip_tuning.so only (scripts/): ceiling-finding builds whose results are meaningless
-            if constexpr (DH == 48 && !ALIBI && DT == VF_BF16) {
+            if constexpr (DH == 48 && !ALIBI && DT == VF_BF16 && !PAD) {
                 static const int dbg = vf_tuning_env("VF_ATTN_DBG", 0);
                 if (dbg == 1) return launch_fwd<48, 2, false, VF_BF16, 1>(P, grid, st);
                 if (dbg == 2) return launch_fwd<48, 2, false, VF_BF16, 2>(P, grid, st);
@@ -1461,9 +1503,9 @@ int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
             // read feeds 4 MFMAs (gene->CRE cross attention at 8 genes: 948 vs 993 us; no gain at one gene, 1376 blocks)
             if constexpr (DH == 48 && !ALIBI) {
                 if ((long)n_seq * P.H * ((max_q + 255) / 256) >= 2048)
-                    return launch_fwd<48, 4, false, DT>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
+                    return launch_fwd<48, 4, false, DT, 0, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
             }
-            return launch_fwd<DH, 2, ALIBI, DT>(P, grid, st);
+            return launch_fwd<DH, 2, ALIBI, DT, 0, PAD>(P, grid, st);
         }
     }
     if constexpr (DH == 96) {
@@ -1471,24 +1513,32 @@ int launch_attn(AttnParams P, int n_seq, int max_q, int max_k, hipStream_t st) {
         // as ONE 128-query block per (window, head) -- two 64-query blocks would each stage all keys: 3.0 -> 3.5 TB/s.  (At
         // dh = 128 the two-group form needs all 256 VGPRs, one wave per SIMD, and is slower: 3.4 -> 3.1 TB/s.)
         if (max_q > 64 && max_q <= 128 && (long)n_seq * P.H >= 1024)
-            return launch_fwd<DH, 2, ALIBI, DT>(P, dim3(set_grid(P, n_seq, 1)), st);
+            return launch_fwd<DH, 2, ALIBI, DT, 0, PAD>(P, dim3(set_grid(P, n_seq, 1)), st);
     }
-    return launch_fwd<DH, 1, ALIBI, DT>(P, dim3(set_grid(P, n_seq, (max_q + 63) / 64)), st);
+    // dh 192 / 256 (padded classes only): the tiled kernel, one query group per wave -- two stages of K / V are 100 / 132 KiB
+    // of LDS (one block per CU), and the O accumulators alone are 48 / 64 registers per query group
+    return launch_fwd<DH, 1, ALIBI, DT, 0, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 63) / 64)), st);
 }
 
 }  // namespace
 
+static bool legacy_dh(int dh) { return dh == 32 || dh == 48 || dh == 64 || dh == 96 || dh == 128; }
+
+// any_dh (vf_attn_varlen_fwd_v3): every multiple of 8 in [8, 256]; the five class head dims take the same path as without it
 template <int DT>
 static int attn_dispatch(const void* q, const void* k, const void* v, void* out, int64_t q_stride,
                          int64_t k_stride, int64_t v_stride, int64_t o_stride, const int32_t* cu_seqlens_q,
                          const int32_t* cu_seqlens_k, int n_seq, int max_seqlen_q, int max_seqlen_k, int H,
                          int dh, const float* alibi_slopes, float scale, int flags, void* stream,
-                         const int64_t* q_rows = nullptr, const int64_t* kv_rows = nullptr) {
+                         const int64_t* q_rows = nullptr, const int64_t* kv_rows = nullptr, bool any_dh = false) {
     const int q_at_start = flags & VF_ATTN_Q_AT_START, q_log2 = (flags & VF_ATTN_Q_LOG2) ? 1 : 0;
     VF_REQUIRE((flags & ~(VF_ATTN_Q_AT_START | VF_ATTN_Q_LOG2)) == 0, "vf_attn_varlen_fwd: unknown flag bits 0x%x", flags);
     VF_REQUIRE(q && k && v && out && cu_seqlens_q, "vf_attn_varlen_fwd: null pointer");
-    VF_REQUIRE(dh == 32 || dh == 48 || dh == 64 || dh == 96 || dh == 128,
-               "vf_attn_varlen_fwd: head_dim %d not supported (32/48/64/96/128)", dh);
+    if (any_dh)
+        VF_REQUIRE(dh >= 8 && dh <= 256 && dh % 8 == 0,
+                   "vf_attn_varlen_fwd_v3: head_dim %d not supported (a multiple of 8 in [8, 256])", dh);
+    else
+        VF_REQUIRE(legacy_dh(dh), "vf_attn_varlen_fwd: head_dim %d not supported (32/48/64/96/128)", dh);
     VF_REQUIRE(H > 0 && H <= 65535 && n_seq >= 0, "vf_attn_varlen_fwd: H=%d n_seq=%d out of range", H, n_seq);
     VF_REQUIRE((long)n_seq * H * ((max_seqlen_q + 63) / 64) < (1L << 31) - 8,
                "vf_attn_varlen_fwd: n_seq * H * ceil(max_seqlen_q / 64) exceeds the grid limit");
@@ -1500,7 +1550,7 @@ static int attn_dispatch(const void* q, const void* k, const void* v, void* out,
     VF_REQUIRE(max_seqlen_k < (1 << 24) && k_stride < (1 << 24) && v_stride < (1 << 24) &&
                    (int64_t)max_seqlen_k * (k_stride > v_stride ? k_stride : v_stride) < (1LL << 31),
                "vf_attn_varlen_fwd: max_seqlen_k * row stride must stay below 2^31 elements");
-    AttnParams P;
+    AttnParamsPad P;
     P.q = (const unsigned short*)q; P.k = (const unsigned short*)k; P.v = (const unsigned short*)v;
     P.out = (unsigned short*)out;
     P.q_stride = q_stride; P.k_stride = k_stride; P.v_stride = v_stride; P.o_stride = o_stride;
@@ -1508,11 +1558,24 @@ static int attn_dispatch(const void* q, const void* k, const void* v, void* out,
     P.slopes = alibi_slopes; P.scale_log2 = q_log2 ? 1.0f : scale * 1.4426950408889634f; P.H = H;
     P.q_at_start = q_at_start ? 1 : 0; P.q_log2 = q_log2;
     P.q_rows = q_rows; P.kv_rows = kv_rows;
+    P.dh = dh;
 #ifdef VF_TUNING
     P.dbg = 0;
 #endif
     hipStream_t st = (hipStream_t)stream;
     const bool alibi = alibi_slopes != nullptr;
+    if (!legacy_dh(dh)) {                            // a padded class (any_dh only)
+#define VF_PAD(C_) return alibi ? launch_attn<C_, true, DT, true>(P, n_seq, max_seqlen_q, max_seqlen_k, st) \
+                                : launch_attn<C_, false, DT, true>(P, n_seq, max_seqlen_q, max_seqlen_k, st)
+        if (dh <= 32) VF_PAD(32);
+        if (dh <= 48) VF_PAD(48);
+        if (dh <= 64) VF_PAD(64);
+        if (dh <= 96) VF_PAD(96);
+        if (dh <= 128) VF_PAD(128);
+        if (dh <= 192) VF_PAD(192);
+        VF_PAD(256);
+#undef VF_PAD
+    }
     switch (dh) {
         case 32: return alibi ? launch_attn<32, true, DT>(P, n_seq, max_seqlen_q, max_seqlen_k, st) : launch_attn<32, false, DT>(P, n_seq, max_seqlen_q, max_seqlen_k, st);
         case 48: return alibi ? launch_attn<48, true, DT>(P, n_seq, max_seqlen_q, max_seqlen_k, st) : launch_attn<48, false, DT>(P, n_seq, max_seqlen_q, max_seqlen_k, st);
@@ -1567,6 +1630,19 @@ extern "C" int vf_attn_varlen_fwd_v2(const void* q, const void* k, const void* v
     VF_REQUIRE(operand_dtype == VF_F16, "vf_attn_varlen_fwd_v2: operand_dtype must be VF_BF16 or VF_F16");
     return attn_dispatch<VF_F16>(q, k, v, out, q_stride, k_stride, v_stride, o_stride, cu_seqlens_q, cu_seqlens_k, n_seq,
                                  max_seqlen_q, max_seqlen_k, H, dh, alibi_slopes, scale, flags, stream);
+}
+
+extern "C" int vf_attn_varlen_fwd_v3(const void* q, const void* k, const void* v, void* out, int64_t q_stride,
+                                     int64_t k_stride, int64_t v_stride, int64_t o_stride, const int32_t* cu_seqlens_q,
+                                     const int32_t* cu_seqlens_k, int n_seq, int max_seqlen_q, int max_seqlen_k, int H,
+                                     int dh, const float* alibi_slopes, float scale, int operand_dtype, int flags,
+                                     void* stream) {
+    if (operand_dtype == VF_BF16)
+        return attn_dispatch<VF_BF16>(q, k, v, out, q_stride, k_stride, v_stride, o_stride, cu_seqlens_q, cu_seqlens_k, n_seq,
+                                      max_seqlen_q, max_seqlen_k, H, dh, alibi_slopes, scale, flags, stream, nullptr, nullptr, true);
+    VF_REQUIRE(operand_dtype == VF_F16, "vf_attn_varlen_fwd_v3: operand_dtype must be VF_BF16 or VF_F16");
+    return attn_dispatch<VF_F16>(q, k, v, out, q_stride, k_stride, v_stride, o_stride, cu_seqlens_q, cu_seqlens_k, n_seq,
+                                 max_seqlen_q, max_seqlen_k, H, dh, alibi_slopes, scale, flags, stream, nullptr, nullptr, true);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

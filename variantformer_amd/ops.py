@@ -521,6 +521,10 @@ def attn_rows_supported(head_dim: int, alibi: bool, n_seq: int, n_heads: int, ma
                                                    int(max_k), ATTN_Q_LOG2 if q_log2 else 0))
 
 
+# head dims with kernels of their own; every other multiple of 8 up to 256 runs the kernels of its class (vf_attn_varlen_fwd_v3)
+ATTN_CLASS_DIMS = (32, 48, 64, 96, 128)
+
+
 def attn_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_q: torch.Tensor, cu_k: torch.Tensor | None,
                 max_q: int, max_k: int, n_heads: int, head_dim: int, slopes: torch.Tensor | None = None,
                 scale: float | None = None, out: torch.Tensor | None = None, q_at_start: bool = False,
@@ -555,10 +559,12 @@ def attn_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_q: torch.T
                                               int(max_k), n_heads, head_dim, _ptr(slopes), float(scale), _dt(q.dtype), flags,
                                               rows.data_ptr(), rows.data_ptr(), _stream()), "vf_attn_varlen_fwd_rows")
             return
-        check(lib.vf_attn_varlen_fwd_v2(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(0), k.stride(0),
-                                        v.stride(0), out.stride(0), cu_q.data_ptr(), _ptr(cu_k), cu_q.numel() - 1, int(max_q),
-                                        int(max_k), n_heads, head_dim, _ptr(slopes), float(scale), _dt(q.dtype), flags,
-                                        _stream()), "vf_attn_varlen_fwd")
+        # the five class head dims keep the v2 entry; any other multiple of 8 up to 256 runs its padded class (v3)
+        fwd = lib.vf_attn_varlen_fwd_v2 if head_dim in ATTN_CLASS_DIMS else lib.vf_attn_varlen_fwd_v3
+        check(fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), q.stride(0), k.stride(0),
+                  v.stride(0), out.stride(0), cu_q.data_ptr(), _ptr(cu_k), cu_q.numel() - 1, int(max_q),
+                  int(max_k), n_heads, head_dim, _ptr(slopes), float(scale), _dt(q.dtype), flags,
+                  _stream()), "vf_attn_varlen_fwd")
     if TIMER is not None:
         def flops():       # 4 * sum_seq(len_q * len_k) * H * dh (QK^T and PV), evaluated after the timed replay
             lq = (cu_q[1:] - cu_q[:-1]).double()
