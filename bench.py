@@ -19,6 +19,12 @@ the ranks by LPT on the FLOP model, every rank runs its shard in batches of <= `
 all-gather reassembles the [256, 54] expression matrix -- strong scaling (total work fixed as N grows); the line also
 carries each rank's busy time (load imbalance).  `--dtype fp16` runs the fp16-operand path (BASELINE configs[4]).
 
+A plain run sets up, runs the W warm-up and K timed steps, writes `--dump-outputs` and prints the line: nothing else.
+`--full` adds what the benchmark measures beside `value`, each after the timed region: the same steps on one stream and
+with the LayerNorm fold off, the per-kernel replay behind `roofline` / `kernel_families`, batches of 8 and 1 gene, the
+strong-scaling pass at N > 1, the host-inclusive product flow, `cpu_baseline` and the trained-like pass; the `--no-*`
+options leave single ones of these out.
+
 Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -441,14 +447,19 @@ def main():
                     help="cfg2 = the headline 1 Mb / 54-tissue gene (weak scaling); cfg3 = 256 ragged genes, LPT shards, "
                          "strong scaling")
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16", help="16-bit operand type (fp32 accumulation)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-cfg3", action="store_true", help="N > 1: skip the extra strong-scaling pass over BASELINE configs[2]")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the host-inclusive product-flow measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside `value` (see the module docstring); "
+                         "a plain run stops after the timed steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true",
+                    help="with --full: skip the per-kernel replay (roofline, kernel_families) and batch_of_8 / batch_of_1")
+    ap.add_argument("--no-cfg3", action="store_true",
+                    help="with --full, N > 1: skip the extra strong-scaling pass over BASELINE configs[2]")
+    ap.add_argument("--no-pipelined", action="store_true", help="with --full: skip the host-inclusive product-flow measurement")
     ap.add_argument("--no-extra-rates", action="store_true",
-                    help="skip value_single_stream / ln_fold_off / trained_like / batch_of_8 / batch_of_1 (the passes after the timed region): "
-                         "the process then runs W + K + K identical steps, which is what the rocprofv3 passes of "
-                         "scripts/run_profile_set.sh profile")
+                    help="with --full: skip value_single_stream / ln_fold_off / trained_like / batch_of_8 / batch_of_1 (the passes "
+                         "after the timed region): with --no-cpu-baseline --no-pipelined the process then runs W + K + K "
+                         "identical steps, which is what the rocprofv3 kernel-trace passes of scripts/run_profile_set.sh profile")
     ap.add_argument("--single-stream", action="store_true",
                     help="runtime.Switches.overlap_cre_stream off for the whole run (the order the per-kernel replay uses): what "
                          "the rocprofv3 --kernel-trace --stats pass profiles, because with two streams a kernel's traced "
@@ -461,6 +472,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:           # a plain run: nothing after the timed steps but --dump-outputs and the line
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_cfg3 = args.no_pipelined = args.no_extra_rates = True
 
     if args.gpus > 1 and "RANK" not in os.environ:        # no launcher around us: start the ranks as a child process
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -505,7 +518,7 @@ def main():
     batch = make_batch(20251205 + rank, [args.n_cre] * G, [args.n_chunks] * G, [tissues] * G, 200)
     flops_step = batch_flops(batch, hp["embedding_dim"], hp["num_layers"], kw["emb_dim"], kw["num_layers"])
     executed_step = batch_flops(batch, hp["embedding_dim"], hp["num_layers"], kw["emb_dim"], kw["num_layers"],
-                                executed_by_reference=True)
+                                executed_by_reference=True) if args.full else None
     owned = [list(range(r * G, (r + 1) * G)) for r in range(world)]
 
     with torch.no_grad():
@@ -655,19 +668,20 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": ("BASELINE configs[1]: full 1.2B-architecture network (%d modulator layers, width %d, %d "
                                     "heads; seq2reg width 512, 8 heads, 6 layers, assumed), random-init weights, 1 Mb "
-                                    "cis-window, %d tissues, 1 donor; one step = %d such genes per GPU (batch_of_8 / "
-                                    "batch_of_1 beside it)" % (kw["num_layers"], kw["emb_dim"], kw["num_heads"],
-                                                               len(tissues), G)),
+                                    "cis-window, %d tissues, 1 donor; one step = %d such genes per GPU%s"
+                                    % (kw["num_layers"], kw["emb_dim"], kw["num_heads"], len(tissues), G,
+                                       " (batch_of_8 / batch_of_1 beside it)" if small else "")),
                        "genes_per_step_per_gpu": G, "n_cre_windows": args.n_cre, "gene_chunks": args.n_chunks,
                        "tissues": len(tissues), "tokens_per_window": 200, "parallelism": f"gene-shard x{world}",
                        "streams": "one (--single-stream)" if args.single_stream else "CRE layers on a side stream (default)"},
             "algorithmic_tflop_per_gene": round(flops_step / G / 1e12, 3),
-            "reference_executed_tflop_per_gene": round(executed_step / G / 1e12, 3),
             "achieved_algorithmic_tflops_whole_step": round(world * flops_step * args.steps / dt / 1e12, 1),
             "roofline": roof, "kernel_families": kernels, "source_sha": source_sha(),
             "ms_of_each_timed_step_rank0": each_step_ms, "device_allocations_inside_timed_region": allocs_in_timed_region,
             "extra_allocator_priming_passes": extra_warmup,
         }
+        if executed_step is not None:
+            out["reference_executed_tflop_per_gene"] = round(executed_step / G / 1e12, 3)
         if single is not None:
             out["value_single_stream"] = single
         if fold_off is not None:

@@ -6,7 +6,7 @@ for rep in 1 2; do
 for flag in 1 0; do
 python - > gpurun_out/r5b/bench_rows${flag}_$rep.json 2> gpurun_out/r5b/bench_rows${flag}_$rep.err <<P
 import sys
-sys.argv = ["bench.py", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"]
 from variantformer_amd import runtime
 runtime.set_for_this_context(rows_in_attention=bool($flag))
 import bench

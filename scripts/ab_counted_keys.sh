@@ -7,7 +7,7 @@ for rep in 1 2; do
 for form in lowrank counted expanded; do
 python - > gpurun_out/r5e/bench_${form}_$rep.json 2> gpurun_out/r5e/bench_${form}_$rep.err <<P
 import sys
-sys.argv = ["bench.py", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pipelined"]
+sys.argv = ["bench.py", "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pipelined"]
 from variantformer_amd import runtime
 runtime.set_for_this_context(counted_context_keys="$form" != "expanded", lowrank_context="$form" == "lowrank")
 import bench

@@ -6,7 +6,7 @@ for rep in 1 2; do
 for flag in 1 0; do
 python - > gpurun_out/r5d/bench_s${flag}_$rep.json 2> gpurun_out/r5d/bench_s${flag}_$rep.err <<P
 import sys
-sys.argv = ["bench.py", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pipelined"]
+sys.argv = ["bench.py", "--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-pipelined"]
 import variantformer_amd.seq2gene.modules.layers as L
 if not $flag:
     orig = L.ContextFlashAttentionEncoderLayer.self_qkv_of_unique_rows

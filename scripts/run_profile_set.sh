@@ -12,14 +12,14 @@ if [ "$2" != "--skip-tests" ] && [ "$2" != "--pmc-only" ] && [ "$2" != "--prof-o
 fi
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 if [ "$2" != "--pmc-only" ] && [ "$2" != "--prof-only" ]; then
-python bench.py > $O/bench.json 2> $O/bench.err; cat $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; cat $O/bench.json
 fi
 if [ "$2" != "--pmc-only" ]; then
 # kernel stats: W + K + K identical steps in the ONE-stream order (with the CRE side stream a kernel's traced duration includes the
 # time it shares the CUs with the other stream's kernels; `roofline` in every bench line comes from the one-stream replay), and
 # the same command in the default two-stream order beside it
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --no-cpu-baseline --no-extra-rates --no-pipelined --single-stream > $O/bench_prof.json 2> $O/prof.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -- python3 bench.py --no-cpu-baseline --no-extra-rates --no-pipelined > $O/bench_prof_two_streams.json 2> $O/prof2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --no-cpu-baseline --no-extra-rates --no-pipelined --single-stream > $O/bench_prof.json 2> $O/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -- python3 bench.py --full --no-cpu-baseline --no-extra-rates --no-pipelined > $O/bench_prof_two_streams.json 2> $O/prof2.err
 cp $(find $O/prof2 -name '*kernel_stats.csv' | head -1) $O/kernel_stats_two_streams.csv 2>/dev/null; rm -rf $O/prof2
 fi
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/${TAG}_pmc_fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-extra-rates --no-pipelined > $O/pmc_fetch.json 2> $O/pmc_fetch.err
@@ -37,7 +37,7 @@ rm -rf gpurun_out/${TAG}_pmc_fetch gpurun_out/${TAG}_pmc_write gpurun_out/${TAG}
 find $O -name '*kernel_trace.csv' -delete; find $O -name '*.db' -delete
 du -sh $O
 if [ "$2" != "--pmc-only" ] && [ "$2" != "--prof-only" ]; then
-python bench.py --dtype fp16 --no-cpu-baseline --no-pipelined > $O/bench_fp16.json 2>> $O/bench.err
+python bench.py --full --dtype fp16 --no-cpu-baseline --no-pipelined > $O/bench_fp16.json 2>> $O/bench.err
 python bench.py --workload cfg3 --steps 2 --warmup 1 > $O/bench_cfg3_1gpu.json 2>> $O/bench.err
 python scripts/shape_breakdown.py 32 > $O/shape_breakdown.txt 2>&1
 fi
