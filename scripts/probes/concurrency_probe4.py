@@ -2,8 +2,8 @@
 attention kernel (probe 3)?  Run once per library build of scripts/probes/build_probe_libs.py:
     python scripts/probes/concurrency_probe4.py [path/to/libvf_*.so]
 Victims (side stream, 3 launches a round, 5 rounds): LayerNorm consumer 16-bit out (128x128 tiles), N = 320 fp32 (64x64), plain
-GEMM 128x128.  Co-runners (main stream): cross attention on the 32x32x16 kernel, the same on the tiled 16x16x32 kernel
-(VF_ATTN_X32=0), a plain 128x128 GEMM, a LayerNorm-consumer GEMM.  The co-runner's own output is checked too, and the first
+GEMM 128x128.  Co-runners (main stream): cross attention on the 32x32x16 kernel, the same shape with ALiBi slopes on the tiled
+16x16x32 kernel, a plain 128x128 GEMM, a LayerNorm-consumer GEMM.  The co-runner's own output is checked too, and the first
 wrong victim output is dissected: which (row block, column) units, and what the wrong values equal."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -35,14 +35,15 @@ ql, kl = [54 * 201] * G, [1024] * G
 cu_q = torch.tensor([0] + list(np.cumsum(ql)), dtype=torch.int32, device=dev)
 cu_k = torch.tensor([0] + list(np.cumsum(kl)), dtype=torch.int32, device=dev)
 q, kv = rnd(sum(ql), D, scale=0.35).bfloat16(), rnd(sum(kl), 2 * D).bfloat16()
+slopes = torch.tensor([2.0 ** (-(i + 1) / 4) for i in range(H)], device=dev)
 a2, w2, b2 = rnd(54 * 201 * G, K).bfloat16(), (rnd(1536, K) / K ** 0.5).bfloat16(), rnd(1536)
 s2 = ops.ln_stream(rnd(54 * 201 * G, K))
 c2 = rnd(1536)
 
 
 def attn(x32):
-    os.environ["VF_ATTN_X32"] = "1" if x32 else "0"
-    return ops.attn_varlen(q, kv[:, :D], kv[:, D:], cu_q, cu_k, max(ql), max(kl), H, dh, None, q_log2=True)
+    # without ALiBi this shape runs attn_x32_kernel; with it, the tiled attn_fwd_kernel
+    return ops.attn_varlen(q, kv[:, :D], kv[:, D:], cu_q, cu_k, max(ql), max(kl), H, dh, None if x32 else slopes, q_log2=True)
 
 
 corunners = {

@@ -1,6 +1,6 @@
 """Kernels of two HIP streams in flight together give the results they give alone.
 
-Round 6 found (scripts/probes/concurrency_probe3-5.py, pk_hazard_probe.hip, profiles/r06_d_*): a packed-fp32 VALU instruction
+Round 6 found (profiles/r06_d_*, scripts/probes/concurrency_probe{4,5}.py, pk_hazard_probe.hip): a packed-fp32 VALU instruction
 whose op_sel takes the high dword of src1 (v_pk_fma_f32 ... op_sel:[0,1,0]: the LayerNorm-consumer epilogue of gemm_mfma_kernel as
 hipcc's SLP vectoriser emits it) computes with a wrong src1 in lanes 48..63 while a wave of another kernel on the same SIMD issues
 MFMAs -- the output element becomes mean-term + bias, a few units of 16 rows x 1 column per launch beside the cross attention.  The library is therefore built WITHOUT packed-fp32 instructions
@@ -40,13 +40,12 @@ def setup():
         "plain128": lambda: ops.gemm(a, w, b, ops.EPI_BF16, variant=1),
     }
 
+    slopes = torch.tensor([2.0 ** (-(i + 1) / 4) for i in range(H)], device=dev)
+
     def cross(x32):
-        import os
-        os.environ["VF_ATTN_X32"] = "1" if x32 else "0"
-        try:
-            return ops.attn_varlen(q, kv[:, :D], kv[:, D:], cq, ck, max(ql), max(kl), H, dh, None, q_log2=True)
-        finally:
-            os.environ.pop("VF_ATTN_X32", None)
+        # x32: the gene -> CRE cross attention as the model runs it (attn_x32_kernel, v_mfma_f32_32x32x16); otherwise the same
+        # shape with ALiBi slopes, which the dispatch sends to the tiled attn_fwd_kernel (v_mfma_f32_16x16x32)
+        return ops.attn_varlen(q, kv[:, :D], kv[:, D:], cq, ck, max(ql), max(kl), H, dh, None if x32 else slopes, q_log2=True)
     return ops, victims, cross
 
 
@@ -58,6 +57,7 @@ def test_gemm_beside_attention_on_another_stream_is_bit_identical(setup, victim,
     with torch.no_grad():
         ref = f().clone()
         coref = cross(x32).clone()
+        assert ops.last_kernel("attn").startswith("attn_x32_kernel" if x32 else "attn_fwd_kernel"), ops.last_kernel("attn")
         torch.cuda.synchronize()
         main, side = torch.cuda.current_stream(), torch.cuda.Stream()
         for _ in range(4):

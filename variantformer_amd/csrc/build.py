@@ -14,8 +14,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["vf_gemm.hip", "vf_attn.hip", "vf_misc.hip", "vf_bpe.cpp", "vf_vcf.cpp", "vf_host.cpp"]
-HEADERS = ["vf_common.h", os.path.join("..", "..", "include", "vf_hip.h")] + \
-    [os.path.join("tuning", f) for f in ("gemm_persist.inc", "gemm4.inc", "gemm8p.inc", "gemm_xs.inc", "gemm8y.inc", "attn_x32pp.inc")]
+HEADERS = ["vf_common.h", os.path.join("..", "..", "include", "vf_hip.h")]
 LIB = os.path.join(HERE, "libvf_hip.so")
 ARCH = "gfx950"
 # vf_attn: scores are never NaN by construction (finite inputs, -inf only as a mask), so fmaxf needs no
@@ -41,29 +40,18 @@ def _stale() -> bool:
     return any(os.path.getmtime(os.path.join(HERE, f)) > t for f in SOURCES + HEADERS + [os.path.basename(__file__)])   # flags live here
 
 
-TUNING_LIB = os.path.join(HERE, "libvf_hip_tuning.so")
-
-
-def build_lib(force: bool = False, verbose: bool = False, tuning: bool = False) -> str:
-    """tuning=True builds libvf_hip_tuning.so with -DVF_TUNING: the diagnostic kernel variants and the tile sweep of
-    scripts/ (results of the diagnostic variants are meaningless).  The product library never contains them."""
-    if tuning:
-        return _build(TUNING_LIB, ["-DVF_TUNING"], verbose, "tuning_")
+def build_lib(force: bool = False, verbose: bool = False) -> str:
     if not force and not _stale():
         return LIB
-    return _build(LIB, [], verbose, "")
-
-
-def _build(LIB: str, defines: list, verbose: bool, obj_prefix: str) -> str:
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found: cannot build libvf_hip.so")
     objs = []
     procs = []
     for src in SOURCES:
-        obj = os.path.join(HERE, obj_prefix + os.path.splitext(src)[0] + ".o")
+        obj = os.path.join(HERE, os.path.splitext(src)[0] + ".o")
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
-               "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + (NO_PACKED_FP32 if src.endswith(".hip") else []) + defines + \
+               "-mllvm", "-amdgpu-mfma-vgpr-form=1"] + (NO_PACKED_FP32 if src.endswith(".hip") else []) + \
               EXTRA_FLAGS.get(src, []) + \
               ["-c", os.path.join(HERE, src), "-o", obj]
         if verbose:
@@ -85,4 +73,4 @@ def _build(LIB: str, defines: list, verbose: bool, obj_prefix: str) -> str:
 
 
 if __name__ == "__main__":
-    print(build_lib(force="--force" in sys.argv, verbose="-v" in sys.argv, tuning="--tuning" in sys.argv))
+    print(build_lib(force="--force" in sys.argv, verbose="-v" in sys.argv))

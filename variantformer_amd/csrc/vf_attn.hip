@@ -100,13 +100,6 @@ struct AttnParams {
     const int64_t* q_rows;   // optional row maps (vf_attn_varlen_fwd_rows): token t's query row is row q_rows[t] of q, its key /
     const int64_t* kv_rows;  // value rows are row kv_rows[t] of k / v -- the operands are TABLES of distinct rows (the first
                              // layers' projections by lookup) and the gather happens in the loads; null: row t itself
-#if defined(VF_SHORT_PROF) || defined(VF_X32PP_PROF)
-    unsigned long long* prof;   // scripts/probes/attn_*_probe.hip only
-#endif
-#ifdef VF_TUNING
-    int dbg;                    // VF_ATTN_SHORT_DBG (attn_short2_kernel; results meaningless): 1 = loads, LDS staging and stores only
-                                // (no tile arithmetic): the streaming ceiling of the one-block-per-(sequence, head) structure
-#endif
 };
 
 // The padded-class kernels' argument (PAD = true): AttnParams plus the true head dim, a multiple of 8 below the class DH.  A
@@ -149,14 +142,8 @@ __device__ __forceinline__ s16x4_t lds_tr_read(const char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p);
 }
 
-#ifndef VF_ATTN_PV_INTERLEAVE
-#define VF_ATTN_PV_INTERLEAVE 1
-#endif
-
 // One 64-key tile for QG query groups of a wave: S^T = K.Q^T, online softmax, O^T += V^T.P^T.
 // sK / sV point at the tile's first key row in LDS.  All state is per lane (r = query, g = key sub-block).
-// DBGT (diagnostic builds of the long-stream kernel only): 1 = no softmax VALU work (P = S), 2 = additionally no LDS
-// fragment reads (operands reused), used to locate the binding ceiling; results are meaningless.
 // NKT (4, 2 or 1): number of 16-key sub-tiles that can hold a valid key -- the LAST tile of a sequence whose remainder is
 // <= 32 / <= 16 keys runs the 2 / 1 sub-tile form: no K fragments, QK^T MFMAs, bias, maximum, exponentials for the rest, and
 // for NKT <= 2 no second 32-key PV block either.  Bit-identical to the full tile (whose masked keys contribute p = 0 exactly,
@@ -167,7 +154,7 @@ __device__ __forceinline__ s16x4_t lds_tr_read(const char* p) {
 // INTEGER: a power-of-two offset does not move the rounding of p, so modes 1 and 2 produce the same bits -- which is what
 // lets the kernels a query may be served by differ in mode (a gene's result must not depend on the batch geometry that picks
 // the kernel: the tiled kernels run mode 2, the one-block-per-sequence kernel mode 1).
-template <int DH, int QG, bool ALIBI, int DT, int DBGT = 0, int NKT = 4, int SM = 0>
+template <int DH, int QG, bool ALIBI, int DT, int NKT = 4, int SM = 0>
 __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, int kb0, int len_k, int r, int g, float c,
                                           float slope2, const typename Op16<DT>::frag (&qf)[QG][KLayout<DH>::KS], const float (&q_pos)[QG],
                                           f32x4_t (&o)[QG][DH / 16], float (&m_run)[QG], f32x4_t (&l_acc)[QG]) {
@@ -189,13 +176,12 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, int kb
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-            kf[kt][ks] = DBGT >= 2 ? qf[0][ks] : *reinterpret_cast<const frag_t*>(
+            kf[kt][ks] = *reinterpret_cast<const frag_t*>(
                 sK + (16 * kt + r) * K_ROW_BYTES + (((4 * ks + g) ^ KLayout<DH>::swz(r)) << 4));
     auto read_v = [&](int kb, frag_t(&vf)[NDT]) {
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
             const char* vp = sV + (32 * kb + 4 * g + (r >> 2)) * VROW + 32 * dt + 8 * (r & 3);
-            if (DBGT >= 2) { vf[dt] = qf[0][0]; continue; }
             const s16x4_t lo = lds_tr_read(vp);
             const s16x4_t hi = lds_tr_read(vp + 16 * VROW);
             vf[dt] = __builtin_bit_cast(frag_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -251,21 +237,9 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, int kb
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) o[qg][dt] = Op16<DT>::mfma(vf1[dt], pf[qg][1], o[qg][dt]);
         }
-        if (DBGT == 0) {
-            l_acc[qg] = Op16<DT>::mfma(ones, pf[qg][0], l_acc[qg]);
-            if (NKT > 2) l_acc[qg] = Op16<DT>::mfma(ones, pf[qg][1], l_acc[qg]);
-        }
+        l_acc[qg] = Op16<DT>::mfma(ones, pf[qg][0], l_acc[qg]);
+        if (NKT > 2) l_acc[qg] = Op16<DT>::mfma(ones, pf[qg][1], l_acc[qg]);
     };
-    if (DBGT >= 1) {                                  // diagnostic: P = S, no softmax arithmetic
-        read_v(1, vf1);
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg) {
-            pack_p(qg);
-            l_acc[qg] = (f32x4_t){1.f, 1.f, 1.f, 1.f};
-            pv(qg);
-        }
-        return;
-    }
     float m_new[QG];
     bool moved = false;
 #pragma unroll
@@ -344,14 +318,9 @@ __device__ __forceinline__ void attn_tile(const char* sK, const char* sV, int kb
                 for (int e = 0; e < 4; ++e) s[qg][kt][e] = __builtin_amdgcn_exp2f(fmaf(s[qg][kt][e], cc, mc));
         }
         pack_p(qg);
-        if (VF_ATTN_PV_INTERLEAVE && qg > 0) pv(qg - 1);
+        if (qg > 0) pv(qg - 1);
     }
-    if (VF_ATTN_PV_INTERLEAVE) {
-        pv(QG - 1);
-    } else {
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg) pv(qg);
-    }
+    pv(QG - 1);
 }
 
 // The last key tile of a sequence in its short form: `rem` = keys it holds, <= 32 (the caller's tile loop stops one tile
@@ -361,14 +330,14 @@ __device__ __forceinline__ void attn_tile_short(int rem, const char* sK, const c
                                                 float slope2, const typename Op16<DT>::frag (&qf)[QG][KLayout<DH>::KS],
                                                 const float (&q_pos)[QG], f32x4_t (&o)[QG][DH / 16], float (&m_run)[QG],
                                                 f32x4_t (&l_acc)[QG]) {
-    if (rem <= 16) attn_tile<DH, QG, ALIBI, DT, 0, 1, SM>(sK, sV, kb0, len_k, r, g, c, slope2, qf, q_pos, o, m_run, l_acc);
-    else attn_tile<DH, QG, ALIBI, DT, 0, 2, SM>(sK, sV, kb0, len_k, r, g, c, slope2, qf, q_pos, o, m_run, l_acc);
+    if (rem <= 16) attn_tile<DH, QG, ALIBI, DT, 1, SM>(sK, sV, kb0, len_k, r, g, c, slope2, qf, q_pos, o, m_run, l_acc);
+    else attn_tile<DH, QG, ALIBI, DT, 2, SM>(sK, sV, kb0, len_k, r, g, c, slope2, qf, q_pos, o, m_run, l_acc);
 }
 
 // (2 query groups with ALiBi sit at the 170-register edge of three waves per SIMD -- the CRE stream's self attention; the
 // integer-maximum form compiles to 172 without the bound)
 // PAD: a head dim below the class DH (AttnParamsPad::dh, see the file header); classes 192 / 256 exist only in this form.
-template <int DH, int QG, bool ALIBI, int DT = VF_BF16, int DBG = 0, bool QL = false, bool PAD = false>
+template <int DH, int QG, bool ALIBI, int DT = VF_BF16, bool QL = false, bool PAD = false>
 __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) void attn_fwd_kernel(AttnArgs<PAD> P) {
     using frag_t = typename Op16<DT>::frag;
     const int dh = PAD ? pad_dh(P) : DH;               // true head dim: chunks [dh / 8, CPR) of a row are zeros in LDS
@@ -515,25 +484,25 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
     // per SIMD: 172 > 170)
     const bool active = QG > 1 || qb0 + wave * QG * 16 < len_q;       // wave-uniform
     for (int t = 0; t + 1 < nkv; ++t) {
-        if (DBG < 3) load_regs(t + 1);
+        load_regs(t + 1);
         const char* sK = smem + (t & 1) * STAGE;
         if (active)
-            attn_tile<DH, QG, ALIBI, DT, (DBG > 2 ? 0 : DBG), 4, (QL ? 2 : 0)>(sK, sK + K_TILE_BYTES, t * BKV, len_k, r, g, c, slope2, qf,
-                                                           q_pos, o, m_run, l_acc);
-        if (DBG < 3) write_lds((t + 1) & 1, t + 1);
-        if (DBG < 4) __syncthreads();
+            attn_tile<DH, QG, ALIBI, DT, 4, (QL ? 2 : 0)>(sK, sK + K_TILE_BYTES, t * BKV, len_k, r, g, c, slope2, qf, q_pos, o,
+                                                          m_run, l_acc);
+        write_lds((t + 1) & 1, t + 1);
+        __syncthreads();
     }
     if (active) {
         const int t = nkv - 1;
         const char* sK = smem + (t & 1) * STAGE;
         // short sequences (one query group per wave: seq2reg windows of 70-200 tokens, 2-4 tiles): the last tile in its
         // 16 / 32-key form when the remainder allows (a 100-token window: 64 + 36 keys; a 200-token chunk: 3 x 64 + 8)
-        if (QG == 1 && DBG == 0 && len_k - t * BKV <= 32)
+        if (QG == 1 && len_k - t * BKV <= 32)
             attn_tile_short<DH, QG, ALIBI, DT, (QL ? 2 : 0)>(len_k - t * BKV, sK, sK + K_TILE_BYTES, t * BKV, len_k, r, g, c, slope2, qf,
                                                q_pos, o, m_run, l_acc);
         else
-            attn_tile<DH, QG, ALIBI, DT, (DBG > 2 ? 0 : DBG), 4, (QL ? 2 : 0)>(sK, sK + K_TILE_BYTES, t * BKV, len_k, r, g, c, slope2, qf, q_pos,
-                                                           o, m_run, l_acc);
+            attn_tile<DH, QG, ALIBI, DT, 4, (QL ? 2 : 0)>(sK, sK + K_TILE_BYTES, t * BKV, len_k, r, g, c, slope2, qf, q_pos, o,
+                                                          m_run, l_acc);
     }
 
     // ---- normalise and store: lane (r,g) holds O[q = r][d = 16dt + 4g .. +3]
@@ -582,9 +551,6 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
 // end (one block-wide vote) and recomputed with the running-maximum form -- correctness never depends on the range, only
 // the speed of such a block does.  The recomputation uses INTEGER offsets (ceil of the maximum): powers of two commute with
 // the roundings, so both forms round the same probabilities.
-#ifndef VF_X32_WIDE_STORE
-#define VF_X32_WIDE_STORE 1
-#endif
 // PAD: a head dim of 8 ... 40 in the 48 class (AttnParamsPad::dh): columns [dh, 48) of Q, K and V are zeros
 template <int DT, int QB, bool FAST = false, bool PAD = false>
 __global__ __launch_bounds__(256) void attn_x32_kernel(AttnArgs<PAD> P) {
@@ -741,7 +707,7 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnArgs<PAD> P) {
             }
             float mx = max3f(ma, mb, max2f(s[qb][0][15], s[qb][1][15]));
             if (P.q_log2) mx = __builtin_ceilf(mx);      // integer offsets whenever q carries the scale: the recomputation pass
-                                                         // of the FAST kernel and VF_ATTN_NOMAX=0 round what FAST rounds
+                                                         // of the FAST kernel rounds what FAST rounds
             const unsigned u = __float_as_uint(mx);
             auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
             m_new[qb] = max3f(m_run[qb], __uint_as_float(sw[0]), __uint_as_float(sw[1]));   // finite: tile 0 holds a valid key
@@ -835,11 +801,11 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnArgs<PAD> P) {
 
     // ---- normalise and store: lane (q, h) holds O[q][d = 32 dt + (i & 3) + 8 (i >> 2) + 4 h]; the denominator is row
     // d = 48 = element 8 of the dt = 1 tile in the h = 0 lane.
-    // Wide form (16-byte aligned output rows, VF_X32_WIDE_STORE): the wave's 32 QB x 48 block goes through LDS (the K / V stages
+    // Wide form (16-byte aligned output rows): the wave's 32 QB x 48 block goes through LDS (the K / V stages
     // are free: every wave is behind the vote / the barrier that ends the pass) and leaves as whole 96-byte row segments, 16 bytes per lane,
     // ~11 rows per store instruction -- instead of 12 QB eight-byte stores per lane that each touch 32 rows (the store path of
     // the CU is shared with the K / V loads of the co-resident block).  Same values, same bits.
-    const bool wide = VF_X32_WIDE_STORE && ((reinterpret_cast<uintptr_t>(P.out) | (uintptr_t)(P.o_stride * 2)) & 15) == 0;
+    const bool wide = ((reinterpret_cast<uintptr_t>(P.out) | (uintptr_t)(P.o_stride * 2)) & 15) == 0;
     constexpr int OPITCH = DH * 2 + 16;
     char* const oreg = smem + wave * (QB * 32 * OPITCH);
     static_assert(4 * QB * 32 * OPITCH <= 2 * STAGE, "the output staging must fit the K / V stages");
@@ -880,10 +846,6 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnArgs<PAD> P) {
     }
 }
 
-#ifdef VF_TUNING   // attn_x32pp_kernel: anti-phase 8-wave cross attention, 12 % slower (profiles/r04_l)
-#include "tuning/attn_x32pp.inc"
-#endif
-
 // Short sequences (<= 256 queries and keys: seq2reg windows, the gene stream): one block per (sequence, head).
 // The whole K/V of the sequence is staged into LDS once (all loads issued before the first store: one load latency,
 // no per-tile barriers) and is fetched once per (sequence, head) instead of once per 64-query block.
@@ -922,12 +884,6 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
     const int r = lane & 15, g = lane >> 4;
     const int nkv = (len_k + BKV - 1) / BKV;
     const int nchunks = nkv * BKV * 8;
-#ifdef VF_SHORT_PROF
-    unsigned long long pt0 = __builtin_readcyclecounter(), pt1, ptv[5] = {0, 0, 0, 0, 0};
-#define SH_MARK(i) { pt1 = __builtin_readcyclecounter(); ptv[i] = pt1 - pt0; pt0 = pt1; }
-#else
-#define SH_MARK(i)
-#endif
 
     // ---- Q fragments of this wave's query groups (issued before the K/V loads so that both are in flight together)
     frag_t qf[QG][KS];
@@ -964,11 +920,6 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
                 vbuf[it] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)key * P.v_stride + cc * 8);
             }
         }
-        SH_MARK(0)                                   // loads issued
-#ifdef VF_SHORT_PROF
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        SH_MARK(1)                                   // loads landed
-#endif
 #pragma unroll
         for (int it = 0; it < MAXIT; ++it) {
             const int ci = tid + 256 * it;
@@ -993,7 +944,6 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
         for (int dt = 0; dt < NDT; ++dt) o[qg][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     }
     __syncthreads();
-    SH_MARK(2)                                       // LDS written, barrier passed
     if (wave * 16 >= len_q) return;                                // this wave owns no valid query (wave-uniform)
 
     // A wave whose LAST query group lies past the sequence (201 queries = 13 groups of 16 over 4 waves: waves 1-3 own 3
@@ -1006,7 +956,7 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
     const int n_full = rem <= 32 ? tl : nkv;
     if (QG == 1 || last_group_valid) {
         for (int t = 0; t < n_full; ++t)
-            attn_tile<DH, QG, ALIBI, DT, 0, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
+            attn_tile<DH, QG, ALIBI, DT, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
                                                    slope2, qf, q_pos, o, m_run, l_acc);
         if (rem <= 32)
             attn_tile_short<DH, QG, ALIBI, DT, SM>(rem, sK0 + tl * BKV * K_ROW_BYTES, sV0 + tl * BKV * VROW, tl * BKV, len_k,
@@ -1019,14 +969,13 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
         auto& m_run1 = reinterpret_cast<float(&)[Q1]>(m_run);
         auto& l_acc1 = reinterpret_cast<f32x4_t(&)[Q1]>(l_acc);
         for (int t = 0; t < n_full; ++t)
-            attn_tile<DH, Q1, ALIBI, DT, 0, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
+            attn_tile<DH, Q1, ALIBI, DT, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
                                                    slope2, qf1, q_pos1, o1, m_run1, l_acc1);
         if (rem <= 32)
             attn_tile_short<DH, Q1, ALIBI, DT, SM>(rem, sK0 + tl * BKV * K_ROW_BYTES, sV0 + tl * BKV * VROW, tl * BKV, len_k,
                                                    r, g, c, slope2, qf1, q_pos1, o1, m_run1, l_acc1);
     }
 
-    SH_MARK(3)                                       // tiles computed
 #pragma unroll
     for (int qg = 0; qg < QG; ++qg) {
         const float l = l_acc[qg][0];
@@ -1042,16 +991,6 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
             }
         }
     }
-#ifdef VF_SHORT_PROF
-    SH_MARK(4)                                       // stores issued
-    if (lane == 0 && wave == 0 && (blockIdx.x & 63) == 0) {
-        unsigned long long* pp = P.prof + (blockIdx.x >> 6) * 8;
-        for (int i = 0; i < 5; ++i) pp[i] = ptv[i];
-        pp[5] = pt0;                                 // end stamp
-        pp[6] = pt0 - (ptv[0] + ptv[1] + ptv[2] + ptv[3] + ptv[4]);      // start stamp
-    }
-#endif
-#undef SH_MARK
 }
 
 // The same kernel for THREE resident blocks per CU (the gene stream's 201-token sequences).  attn_short_kernel at 4 query
@@ -1170,18 +1109,9 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnArgs<PAD> P, in
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) o[qg][dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         }
-#ifdef VF_TUNING
-        if (P.dbg & 1) {                                           // ceiling probe: keep the Q fragments alive, compute nothing
-#pragma unroll
-            for (int qg = 0; qg < QG; ++qg) {
-                asm volatile("" ::"v"(qf[ps][qg][0]), "v"(qf[ps][qg][1]));
-                l_acc[qg] = (f32x4_t){1.f, 1.f, 1.f, 1.f};
-            }
-        } else
-#endif
         if ((g0 + 4) * 16 < len_q) {                               // both groups hold valid queries
             for (int t = 0; t < n_full; ++t)
-                attn_tile<DH, QG, ALIBI, DT, 0, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
+                attn_tile<DH, QG, ALIBI, DT, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
                                                        slope2, qf[ps], q_pos, o, m_run, l_acc);
             if (rem <= 32)
                 attn_tile_short<DH, QG, ALIBI, DT, SM>(rem, sK0 + tl * BKV * K_ROW_BYTES, sV0 + tl * BKV * VROW, tl * BKV, len_k,
@@ -1193,7 +1123,7 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnArgs<PAD> P, in
             auto& m_run1 = reinterpret_cast<float(&)[1]>(m_run);
             auto& l_acc1 = reinterpret_cast<f32x4_t(&)[1]>(l_acc);
             for (int t = 0; t < n_full; ++t)
-                attn_tile<DH, 1, ALIBI, DT, 0, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
+                attn_tile<DH, 1, ALIBI, DT, 4, SM>(sK0 + t * BKV * K_ROW_BYTES, sV0 + t * BKV * VROW, t * BKV, len_k, r, g, c,
                                                       slope2, qf1, q_pos1, o1, m_run1, l_acc1);
             if (rem <= 32)
                 attn_tile_short<DH, 1, ALIBI, DT, SM>(rem, sK0 + tl * BKV * K_ROW_BYTES, sV0 + tl * BKV * VROW, tl * BKV, len_k,
@@ -1216,11 +1146,6 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnArgs<PAD> P, in
     }
 }
 
-// A/B toggles of the one-block-per-sequence kernels, read ONCE per process and shared by the dispatch (launch_attn) and by
-// rows_supported, which must agree on every geometry (round-5 advice: rows_supported re-read them on every call)
-static int env_short2() { static const int v = vf_tuning_env("VF_ATTN_SHORT2", 1); return v; }      // 0: the one-pass kernel
-static int env_short64() { static const int v = vf_tuning_env("VF_ATTN_SHORT64", 1); return v; }    // 0: the tiled kernel at dh 64
-
 // Only attn_short2_kernel's ROWS instantiations read AttnParams::q_rows / kv_rows: every other launcher refuses a row map
 // instead of silently attending over the wrong rows (round-5 advice).
 static int no_row_map(const AttnParams& P, const char* kernel) {
@@ -1241,9 +1166,9 @@ static unsigned set_grid(AttnParams& P, int n_seq, int nqb) {
 // dynamic LDS of the tiled kernel: two (K tile + V tile) stages
 template <int DH> constexpr int attn_fwd_lds() { return 2 * (KLayout<DH>::TILE + VLayout<DH>::TILE); }
 
-template <int DH, int QG, bool ALIBI, int DT, int DBG, bool QL, bool PAD>
+template <int DH, int QG, bool ALIBI, int DT, bool QL, bool PAD>
 int launch_fwd_k(const AttnParamsPad& P, dim3 grid, hipStream_t st) {
-    auto kern = attn_fwd_kernel<DH, QG, ALIBI, DT, DBG, QL, PAD>;
+    auto kern = attn_fwd_kernel<DH, QG, ALIBI, DT, QL, PAD>;
     constexpr int lds = attn_fwd_lds<DH>();
     if (lds > 65536) {                             // dh >= 128: above the default dynamic-LDS limit (dh 256: 132 KiB)
         static bool attr_set[VF_MAX_DEVICES] = {};
@@ -1265,11 +1190,11 @@ int launch_fwd_k(const AttnParamsPad& P, dim3 grid, hipStream_t st) {
 }
 
 // q carrying the softmax scale (AttnParams::q_log2) selects the integer-maximum instantiation (attn_tile mode 2)
-template <int DH, int QG, bool ALIBI, int DT, int DBG = 0, bool PAD = false>
+template <int DH, int QG, bool ALIBI, int DT, bool PAD = false>
 int launch_fwd(const AttnParamsPad& P, dim3 grid, hipStream_t st) {
     if (const int rc = no_row_map(P, "attn_fwd_kernel")) return rc;
-    if (DBG == 0 && P.q_log2) return launch_fwd_k<DH, QG, ALIBI, DT, 0, true, PAD>(P, grid, st);
-    return launch_fwd_k<DH, QG, ALIBI, DT, DBG, false, PAD>(P, grid, st);
+    if (P.q_log2) return launch_fwd_k<DH, QG, ALIBI, DT, true, PAD>(P, grid, st);
+    return launch_fwd_k<DH, QG, ALIBI, DT, false, PAD>(P, grid, st);
 }
 
 template <int DH, int QG, bool ALIBI, int DT, bool QL, bool PAD>
@@ -1322,15 +1247,6 @@ int launch_short2_k(AttnParamsPad P, int n_seq, int max_k, hipStream_t st) {
     const unsigned nblk = set_grid(P, n_seq, 1);
     vf_note_kernel(1, ROWS ? (NPASS == 1 ? "attn_short2_kernel<1 pass,rows>" : "attn_short2_kernel<2 passes,rows>")
                            : (NPASS == 1 ? "attn_short2_kernel<1 pass>" : "attn_short2_kernel<2 passes>"));
-#ifdef VF_TUNING
-    P.dbg = vf_tuning_env("VF_ATTN_SHORT_DBG", 0);
-    const int lds_probe = vf_tuning_env("VF_ATTN_SHORT_LDS", 0);     // occupancy probe: request this many bytes instead (>= lds)
-    if (lds_probe > lds) {
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds_probe, st, static_cast<const AttnArgs<PAD>&>(P), kr);
-        VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
-        return VF_OK;
-    }
-#endif
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, static_cast<const AttnArgs<PAD>&>(P), kr);
     VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
     return VF_OK;
@@ -1360,35 +1276,13 @@ template <int DT, int QB, bool PAD = false>
 int launch_x32(const AttnParamsPad& P, dim3 grid, hipStream_t st) {
     if (const int rc = no_row_map(P, "attn_x32_kernel")) return rc;
     constexpr int lds = 2 * BKV * (112 + 192);
-    static const int nomax = vf_tuning_env("VF_ATTN_NOMAX", 1);    // 0: running maximum always (A/B)
     vf_note_kernel(1, QB == 2 ? "attn_x32_kernel<64 queries per wave>" : "attn_x32_kernel<32 queries per wave>");
     const AttnArgs<PAD>& A = P;
-    if (P.q_log2 && nomax) hipLaunchKernelGGL((attn_x32_kernel<DT, QB, true, PAD>), grid, dim3(256), lds, st, A);
+    if (P.q_log2) hipLaunchKernelGGL((attn_x32_kernel<DT, QB, true, PAD>), grid, dim3(256), lds, st, A);
     else hipLaunchKernelGGL((attn_x32_kernel<DT, QB, false, PAD>), grid, dim3(256), lds, st, A);
     VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
     return VF_OK;
 }
-
-#ifdef VF_TUNING
-template <int DT>
-int launch_x32pp(const AttnParams& P, dim3 grid, hipStream_t st) {
-    constexpr int lds = 4 * BKV * (112 + 192);                      // 77 824 bytes: above the default dynamic-LDS limit
-    auto kern = attn_x32pp_kernel<DT>;
-    static bool attr_set[VF_MAX_DEVICES] = {};
-    const int dev = vf_current_device();
-    if (dev < 0 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            (void)hipGetLastError();
-            vf_set_error("vf_attn_varlen_fwd: cannot reserve %d bytes of LDS", lds);
-            return VF_ERR_LAUNCH;
-        }
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, P);
-    VF_CHECK_LAUNCH("vf_attn_varlen_fwd");
-    return VF_OK;
-}
-#endif
 
 // Geometries the row-map form (AttnParams::q_rows / kv_rows) serves: exactly those launch_attn sends to attn_short2_kernel
 // in the model's call form -- seq2reg windows / chunks (dh 64, no bias) and the gene stream's self attention (dh 48, ALiBi,
@@ -1399,9 +1293,9 @@ static bool rows_supported(int dh, bool alibi, long n_seq, int H, int max_q, int
     short2_rows(max_k, kr, vr);
     // (exactly launch_attn's conditions, in its order: a geometry it sends elsewhere has no row map)
     if (dh == 48 && alibi)
-        return max_q > 128 && env_short2() && 3 * (kr * KLayout<48>::ROW + vr * VLayout<48>::ROW) <= 160 * 1024;
+        return max_q > 128 && 3 * (kr * KLayout<48>::ROW + vr * VLayout<48>::ROW) <= 160 * 1024;
     if (dh == 64 && !alibi) {
-        if (!env_short64() || n_seq * H < 1024) return false;
+        if (n_seq * H < 1024) return false;
         const int image = kr * KLayout<64>::ROW + vr * VLayout<64>::ROW;
         if (max_q <= 128 && max_k <= 128) return 3 * image <= 160 * 1024;
         if (max_q > 128) return 2 * image <= 160 * 1024;          // (<= 256 both: checked above)
@@ -1431,29 +1325,17 @@ int launch_attn(AttnParamsPad P, int n_seq, int max_q, int max_k, hipStream_t st
     // query, never the arithmetic of a query: tests test_cfg3 / test_headline batch independence at 1e-5).  64 queries
     // per wave once that leaves >= 8 blocks per CU (the batched gene -> CRE cross attention), else 32 (3 waves / SIMD).
     if constexpr (DH == 48 && !ALIBI) {
-        const int x32 = vf_tuning_env("VF_ATTN_X32", 1);             // 0: the 16x16x32 kernels (A/B; read per launch in the tuning library)
-        if (x32) {
-#ifdef VF_TUNING   // VF_ATTN_X32PP=1: the anti-phase experiment (attn_x32pp_kernel: slower, see its header; class dh only)
-            if constexpr (!PAD) {
-                static const int pp = vf_tuning_env("VF_ATTN_X32PP", 0);
-                static const int nomax = vf_tuning_env("VF_ATTN_NOMAX", 1);
-                if (pp != 0 && nomax != 0 && x32 != 2 && P.q_log2 && (long)n_seq * P.H * ((max_q + 511) / 512) >= 1024)
-                    return launch_x32pp<DT>(P, dim3(set_grid(P, n_seq, (max_q + 511) / 512)), st);
-            }
-#endif
-            if (x32 != 2 && (long)n_seq * P.H * ((max_q + 255) / 256) >= 2048)
-                return launch_x32<DT, 2, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
-            return launch_x32<DT, 1, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 127) / 128)), st);
-        }
+        if ((long)n_seq * P.H * ((max_q + 255) / 256) >= 2048)
+            return launch_x32<DT, 2, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
+        return launch_x32<DT, 1, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 127) / 128)), st);
     }
     if constexpr (DH <= 48) {
         if (max_q > 128 && max_q <= 256 && max_k <= 256) {
             // three resident blocks per CU (two passes of 2 query groups, trimmed LDS image) once the image leaves room
-            // for them; VF_ATTN_SHORT2=0: the one-pass kernel (A/B)
-            const int short2 = env_short2();
+            // for them
             int kr, vr;
             short2_rows(max_k, kr, vr);
-            if (short2 && 3 * (kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW) <= 160 * 1024)
+            if (3 * (kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW) <= 160 * 1024)
                 return launch_short2<DH, ALIBI, DT, 2, PAD>(P, n_seq, max_k, st);
             if (max_q <= 192) return launch_short<DH, 3, ALIBI, DT, PAD>(P, n_seq, max_k, st);
             return launch_short<DH, 4, ALIBI, DT, PAD>(P, n_seq, max_k, st);
@@ -1461,11 +1343,10 @@ int launch_attn(AttnParamsPad P, int n_seq, int max_q, int max_k, hipStream_t st
     }
     if constexpr (DH == 64 || DH == 32) {
         // seq2reg windows (<= 128 tokens at dh = 64: a 36 KB image): one block per (window, head) with the whole K / V in
-        // LDS instead of two 64-query blocks that each fetch K / V and wait for it (VF_ATTN_SHORT64=0: the tiled kernel).
+        // LDS instead of two 64-query blocks that each fetch K / V and wait for it.
         // dh = 32 (a tokenizer geometry the real checkpoint might have, scripts/s2r_dims_sweep.py) takes the same kernel
         // since round 6: the tiled kernel ran its windows at 3.2 TB/s against 4.1 for dh = 64.
-        const int short64 = env_short64();
-        if (short64 && max_q <= 128 && max_k <= 128 && (long)n_seq * P.H >= 1024) {
+        if (max_q <= 128 && max_k <= 128 && (long)n_seq * P.H >= 1024) {
             int kr, vr;
             short2_rows(max_k, kr, vr);
             if (3 * (kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW) <= 160 * 1024)
@@ -1473,8 +1354,8 @@ int launch_attn(AttnParamsPad P, int n_seq, int max_q, int max_k, hipStream_t st
         }
         // 129-256-token chunks (seq2reg's 200-token gene chunks): the same kernel in its two-pass form, one block per (chunk,
         // head) with a 62 KB image (two resident blocks per CU) instead of four 64-query blocks of the tiled kernel that each
-        // stage all keys: 1544 -> 1329 us per launch at 32 genes, bit-identical (profiles/r04_k; VF_ATTN_SHORT64=0: tiled kernel)
-        if (DH == 64 && short64 && max_q > 128 && max_q <= 256 && max_k <= 256 && (long)n_seq * P.H >= 1024) {
+        // stage all keys: 1544 -> 1329 us per launch at 32 genes, bit-identical (profiles/r04_k)
+        if (DH == 64 && max_q > 128 && max_q <= 256 && max_k <= 256 && (long)n_seq * P.H >= 1024) {
             int kr, vr;
             short2_rows(max_k, kr, vr);
             if (2 * (kr * KLayout<DH>::ROW + vr * VLayout<DH>::ROW) <= 160 * 1024)
@@ -1490,22 +1371,15 @@ int launch_attn(AttnParamsPad P, int n_seq, int max_q, int max_k, hipStream_t st
     if constexpr (DH <= 64) {
         if (max_q > 256 && (long)n_seq * P.H * ((max_q + 127) / 128) >= 1024) {
             const dim3 grid(set_grid(P, n_seq, (max_q + 127) / 128));
-#ifdef VF_TUNING                                   // libvf_hip_tuning.so only (scripts/): ceiling-finding builds whose results are meaningless
-            if constexpr (DH == 48 && !ALIBI && DT == VF_BF16 && !PAD) {
-                static const int dbg = vf_tuning_env("VF_ATTN_DBG", 0);
-                if (dbg == 1) return launch_fwd<48, 2, false, VF_BF16, 1>(P, grid, st);
-                if (dbg == 2) return launch_fwd<48, 2, false, VF_BF16, 2>(P, grid, st);
-                if (dbg == 3) return launch_fwd<48, 2, false, VF_BF16, 3>(P, grid, st);
-                if (dbg == 4) return launch_fwd<48, 2, false, VF_BF16, 4>(P, grid, st);
-            }
-#endif
             // 4 query groups per wave (256-query blocks) once that still leaves >= 8 blocks per CU: every K/V fragment
-            // read feeds 4 MFMAs (gene->CRE cross attention at 8 genes: 948 vs 993 us; no gain at one gene, 1376 blocks)
+            // read feeds 4 MFMAs (gene->CRE cross attention at 8 genes: 948 vs 993 us; no gain at one gene, 1376 blocks).
+            // (That geometry now returns through attn_x32_kernel above, so this branch is not taken; its kernels stay in the
+            // library until a change of its own removes them.)
             if constexpr (DH == 48 && !ALIBI) {
                 if ((long)n_seq * P.H * ((max_q + 255) / 256) >= 2048)
-                    return launch_fwd<48, 4, false, DT, 0, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
+                    return launch_fwd<48, 4, false, DT, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 255) / 256)), st);
             }
-            return launch_fwd<DH, 2, ALIBI, DT, 0, PAD>(P, grid, st);
+            return launch_fwd<DH, 2, ALIBI, DT, PAD>(P, grid, st);
         }
     }
     if constexpr (DH == 96) {
@@ -1513,11 +1387,11 @@ int launch_attn(AttnParamsPad P, int n_seq, int max_q, int max_k, hipStream_t st
         // as ONE 128-query block per (window, head) -- two 64-query blocks would each stage all keys: 3.0 -> 3.5 TB/s.  (At
         // dh = 128 the two-group form needs all 256 VGPRs, one wave per SIMD, and is slower: 3.4 -> 3.1 TB/s.)
         if (max_q > 64 && max_q <= 128 && (long)n_seq * P.H >= 1024)
-            return launch_fwd<DH, 2, ALIBI, DT, 0, PAD>(P, dim3(set_grid(P, n_seq, 1)), st);
+            return launch_fwd<DH, 2, ALIBI, DT, PAD>(P, dim3(set_grid(P, n_seq, 1)), st);
     }
     // dh 192 / 256 (padded classes only): the tiled kernel, one query group per wave -- two stages of K / V are 100 / 132 KiB
     // of LDS (one block per CU), and the O accumulators alone are 48 / 64 registers per query group
-    return launch_fwd<DH, 1, ALIBI, DT, 0, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 63) / 64)), st);
+    return launch_fwd<DH, 1, ALIBI, DT, PAD>(P, dim3(set_grid(P, n_seq, (max_q + 63) / 64)), st);
 }
 
 }  // namespace
@@ -1559,9 +1433,6 @@ static int attn_dispatch(const void* q, const void* k, const void* v, void* out,
     P.q_at_start = q_at_start ? 1 : 0; P.q_log2 = q_log2;
     P.q_rows = q_rows; P.kv_rows = kv_rows;
     P.dh = dh;
-#ifdef VF_TUNING
-    P.dbg = 0;
-#endif
     hipStream_t st = (hipStream_t)stream;
     const bool alibi = alibi_slopes != nullptr;
     if (!legacy_dh(dh)) {                            // a padded class (any_dh only)

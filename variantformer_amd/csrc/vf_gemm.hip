@@ -18,15 +18,6 @@
 #include <type_traits>
 #include "vf_common.h"
 
-#ifndef VF_G8X_WIDE
-#define VF_G8X_WIDE 1            // persistent kernel, 16-bit-residual producers: 8-column read-back (0: the 4-column form; A/B builds)
-#endif
-#ifndef VF_G8_RES_ALL
-#define VF_G8_RES_ALL 0          // gemm8_kernel, 16-bit residual: 1 = request every epilogue pass's residual rows up front.
-                                 // Measured (profiles/r03_i_producer_epilogue_experiments.log): 417 -> 422 ... 435 us on the gene
-                                 // out-projection -- the epilogue is not waiting for its residual; left off.
-#endif
-
 namespace {
 
 // Bank-conflict swizzle of a [rows][BK] bf16 tile read with ds_read_b128 by lane (r = row & 15, g):
@@ -104,8 +95,7 @@ __device__ __forceinline__ float dpp_f32(float v) {
 // lane's 16-bit values and its part's (sum, M2 about the part mean) go
 template <int DT>
 __device__ __forceinline__ void ln_emit(f32x4_t f, bool valid, unsigned short* p16, float* ppart, int lane,
-                                        float x16_scale = 1.0f, bool st16 = true, bool stpart = true,
-                                        unsigned short* pt16 = nullptr, float t16_scale = 1.0f) {
+                                        float x16_scale = 1.0f, unsigned short* pt16 = nullptr, float t16_scale = 1.0f) {
     // no masking of the sums: N % 32 == 0 (checked at launch), so the 8 lanes of a part are all inside the matrix or
     // all outside, and a row past M only ever feeds its own (never stored) part
     float s1 = (f[0] + f[1]) + (f[2] + f[3]);
@@ -134,8 +124,8 @@ __device__ __forceinline__ void ln_emit(f32x4_t f, bool valid, unsigned short* p
         if (DT == VF_F16) f *= x16_scale;                 // statistics above are those of the UNSCALED row
         pk[0] = Op16<DT>::pack2(f[0], f[1]);
         pk[1] = Op16<DT>::pack2(f[2], f[3]);
-        if (st16) *reinterpret_cast<u32x2_t*>(p16) = pk;
-        if (stpart && (lane & 7) == 0) *reinterpret_cast<f32x2_t*>(ppart) = (f32x2_t){s1, s2};
+        *reinterpret_cast<u32x2_t*>(p16) = pk;
+        if ((lane & 7) == 0) *reinterpret_cast<f32x2_t*>(ppart) = (f32x2_t){s1, s2};
     }
 }
 
@@ -143,22 +133,19 @@ __device__ __forceinline__ void ln_emit(f32x4_t f, bool valid, unsigned short* p
 // consecutive lanes): one 16-byte store per 16-bit copy instead of two 8-byte ones.  The sums run through the SAME balanced
 // tree as ln_emit's (4 values in a lane, then lane pairs, quads, the two quads of a part): fa / fb are what two neighbouring
 // lanes hold there and IEEE addition commutes, so (sum, M2) are bit-identical to the 4-column form.
-template <int DT, int SKIP = 0>      // SKIP (probe builds): 1 = no statistics store, 2 = no 16-bit store, 16 = no statistics arithmetic
+template <int DT>
 __device__ __forceinline__ void ln_emit8(f32x4_t fa, f32x4_t fb, bool valid, unsigned short* p16, float* ppart, int lane,
                                          float x16_scale, unsigned short* pt16, float t16_scale) {
     float s1 = ((fa[0] + fa[1]) + (fa[2] + fa[3])) + ((fb[0] + fb[1]) + (fb[2] + fb[3]));
-    float s2 = s1;
-    if (!(SKIP & 16)) {
     s1 += dpp_f32<0xB1>(s1);                 // lane j <-> j ^ 1: ln_emit's quad_perm [2,3,0,1] step
     s1 += dpp_f32<0x4E>(s1);                 // lane j <-> j ^ 2: ln_emit's row_half_mirror step (the part's two halves)
     const float mp = s1 * (1.0f / 32.0f);
     const float a0 = fa[0] - mp, a1 = fa[1] - mp, a2 = fa[2] - mp, a3 = fa[3] - mp;
     const float b0 = fb[0] - mp, b1 = fb[1] - mp, b2 = fb[2] - mp, b3 = fb[3] - mp;
-    s2 = __builtin_fmaf(a3, a3, __builtin_fmaf(a2, a2, __builtin_fmaf(a1, a1, a0 * a0))) +
-         __builtin_fmaf(b3, b3, __builtin_fmaf(b2, b2, __builtin_fmaf(b1, b1, b0 * b0)));
+    float s2 = __builtin_fmaf(a3, a3, __builtin_fmaf(a2, a2, __builtin_fmaf(a1, a1, a0 * a0))) +
+               __builtin_fmaf(b3, b3, __builtin_fmaf(b2, b2, __builtin_fmaf(b1, b1, b0 * b0)));
     s2 += dpp_f32<0xB1>(s2);
     s2 += dpp_f32<0x4E>(s2);
-    }
     if (valid) {
         u32x4_t pk;
         if (pt16) {                                       // the fp16 trunk copy (VF_LN_PRODUCER_T16)
@@ -169,10 +156,9 @@ __device__ __forceinline__ void ln_emit8(f32x4_t fa, f32x4_t fb, bool valid, uns
         if (DT == VF_F16) { fa *= x16_scale; fb *= x16_scale; }           // statistics above are those of the UNSCALED row
         pk = (u32x4_t){Op16<DT>::pack2(fa[0], fa[1]), Op16<DT>::pack2(fa[2], fa[3]), Op16<DT>::pack2(fb[0], fb[1]),
                        Op16<DT>::pack2(fb[2], fb[3])};
-        if (!(SKIP & 2)) *reinterpret_cast<u32x4_t*>(p16) = pk;
-        else asm volatile("" :: "v"(pk));
-        if (!(SKIP & 1) && (lane & 3) == 0) *reinterpret_cast<f32x2_t*>(ppart) = (f32x2_t){s1, s2};
-        else asm volatile("" :: "v"(s1), "v"(s2));
+        *reinterpret_cast<u32x4_t*>(p16) = pk;
+        if ((lane & 3) == 0) *reinterpret_cast<f32x2_t*>(ppart) = (f32x2_t){s1, s2};
+        else asm volatile("" :: "v"(s1), "v"(s2));     // emits nothing, but the measured register allocation depends on it
     }
 }
 
@@ -181,7 +167,7 @@ __device__ __forceinline__ void ln_emit8(f32x4_t fa, f32x4_t fb, bool valid, uns
 // rows exactly as before, but a lane reads back EIGHT consecutive columns (two ds_read_b128) of a row instead of four, so the
 // residual load, the 16-bit copy, the fp16 trunk copy and the part statistics are 16-byte-per-lane operations on 8 rows per
 // wave-instruction: half the global memory instructions (and pointer steps) for the same bytes.  The producer epilogue was
-// 19-21 k cycles per tile against ~6 k of vector issue (scripts/probes/gemm8x_probe.hip): 288 global memory instructions of
+// 19-21 k cycles per tile against ~6 k of vector issue (profiles/r04_g_gemm8x_tile_phases.log): 288 global memory instructions of
 // 512 bytes per wave through the CU's one address / store path.  Same arithmetic, same summation tree: bit-identical.
 template <int DT, int LN, int REGION>
 __device__ __forceinline__ void producer16_epilogue_wide(f32x4_t (&acc)[4][8], char* region, const char* side, int side_n,
@@ -215,11 +201,7 @@ __device__ __forceinline__ void producer16_epilogue_wide(f32x4_t (&acc)[4][8], c
             const int j = ps * NI + k;
             const char* rp = (j * RI < rows_left) ? res_run : res_last;
             res_run += res_step;
-#if defined(VF_WIDE_SKIP) && (VF_WIDE_SKIP & 4)
-            dst[k] = (u32x4_t){(unsigned)(uintptr_t)rp, 0u, 0u, 0u};
-#else
             dst[k] = *reinterpret_cast<const u32x4_t*>(rp);
-#endif
         }
     };
     auto res_value = [&](u32x2_t v) -> f32x4_t {         // see gemm8_kernel
@@ -239,22 +221,15 @@ __device__ __forceinline__ void producer16_epilogue_wide(f32x4_t (&acc)[4][8], c
         for (int iml = 0; iml < IMP; ++iml) {
             const int im = ps * IMP + iml;
             char* rowp = region + (iml * 16 + r) * PITCH;
-#if !(defined(VF_WIDE_SKIP) && (VF_WIDE_SKIP & 8))
 #pragma unroll
             for (int in = 0; in < TN; ++in) *reinterpret_cast<f32x4_t*>(rowp + (in * 16 + 4 * g) * 4) = acc[in][im] + bvec[in];
-#endif
         }
         u32x4_t da[NI], db[NI];
 #pragma unroll
         for (int k = 0; k < NI; ++k) {
             const char* p = region + (k * RI + ep_row) * PITCH + (lane & 7) * 32;
-#if defined(VF_WIDE_SKIP) && (VF_WIDE_SKIP & 8)
-            da[k] = __builtin_bit_cast(u32x4_t, acc[k & 3][ps * IMP]);          // no LDS read-back (wrong values)
-            db[k] = __builtin_bit_cast(u32x4_t, acc[k & 3][ps * IMP + 1]);
-#else
             da[k] = *reinterpret_cast<const u32x4_t*>(p);
             db[k] = *reinterpret_cast<const u32x4_t*>(p + 16);
-#endif
         }
 #pragma unroll
         for (int k = 0; k < NI; ++k) {
@@ -263,11 +238,7 @@ __device__ __forceinline__ void producer16_epilogue_wide(f32x4_t (&acc)[4][8], c
             const f32x4_t fa = __builtin_bit_cast(f32x4_t, da[k]) + res_value((u32x2_t){rv[0], rv[1]});
             const f32x4_t fb = __builtin_bit_cast(f32x4_t, db[k]) + res_value((u32x2_t){rv[2], rv[3]});
             const bool ok = j * RI + ep_row < WT_M && j * RI < rows_left && ep_col < N;
-#ifdef VF_WIDE_SKIP   // cost-centre probes (scripts/probes/gemm8x_probe.hip builds only; results meaningless)
-            ln_emit8<DT, VF_WIDE_SKIP>(fa, fb, ok, o16_run, part_run, lane, ln.x16_scale, (T16 && ln.t16_out) ? t16_run : nullptr, ln.t16_scale);
-#else
             ln_emit8<DT>(fa, fb, ok, o16_run, part_run, lane, ln.x16_scale, (T16 && ln.t16_out) ? t16_run : nullptr, ln.t16_scale);
-#endif
             o16_run += o16_step;
             part_run += RI * 2;
             if (T16) t16_run += t16_step;
@@ -327,9 +298,7 @@ struct Cfg {
     static_assert(STAGES >= 2 && STAGES <= 5 && (STAGES - 2) * LPT <= 48, "vmcnt range");
 };
 
-// DBG (diagnostic builds only, never selected automatically): 1 = no global loads (fragment reads + MFMA ceiling),
-// 2 = no fragment reads / MFMA (LDS-DMA fill ceiling).  Results are meaningless in both.
-template <class C, int EPI, int DT = VF_BF16, int DBG = 0, int LN = VF_LN_NONE>
+template <class C, int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
 __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned short* __restrict__ A, int64_t lda,
                                                               const unsigned short* __restrict__ W,
                                                               const float* __restrict__ bias,
@@ -383,7 +352,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
     char* const ldsW_piece = smem + C::A_BYTES + wave * C::PW * 1024;
 
     auto issue = [&](int kt, int stage) {
-        if (DBG == 1 || DBG == 3) return;
 #pragma unroll
         for (int i = 0; i < C::PA; ++i) glds16(srcA[i] + kt * BK, ldsA_piece + stage * C::STAGE_BYTES + i * 1024);
 #pragma unroll
@@ -402,7 +370,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
     const int offA = (wm * (BM / C::WM) + r) * ROW_BYTES;
 
     auto read_frags = [&](int stage, int ks, frag_t(&wf)[TN], frag_t(&af)[TM]) {
-        if (DBG == 2) return;
         const char* base = smem + stage * C::STAGE_BYTES + (((4 * ks + g) ^ sw) << 4);
 #pragma unroll
         for (int i = 0; i < TN; ++i) wf[i] = *reinterpret_cast<const frag_t*>(base + offW + i * 16 * ROW_BYTES);
@@ -430,7 +397,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
             }
     };
     auto mma = [&](const frag_t(&wf)[TN], const frag_t(&af)[TM]) {
-        if (DBG == 2) return;
 #pragma unroll
         for (int in = 0; in < TN; ++in)
 #pragma unroll
@@ -464,11 +430,9 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
     int stage = 0;
     // cross from tile t (in `stage`) to tile t+1
     auto boundary = [&](int t) {
-        if (DBG != 3) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            wait_tiles((nkt - 2 - t) < (STAGES - 2) ? (nkt - 2 - t) : (STAGES - 2));
-            __builtin_amdgcn_s_barrier();
-        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_tiles((nkt - 2 - t) < (STAGES - 2) ? (nkt - 2 - t) : (STAGES - 2));
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (t + STAGES < nkt) issue(t + STAGES, stage);
         stage = stage + 1 == STAGES ? 0 : stage + 1;
@@ -542,7 +506,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
     // sub-step instead of being issued as a burst behind the barrier, where they queue in front of the fragment
     // reads (+3...6 % on the K = 1536 shapes).  Neutral to slightly negative on the 4-wave 128x128 tile, which keeps
     // the burst.
-    constexpr bool SPREAD = C::KS == 2 && C::NW == 8 && STAGES == 2 && (TN * TM) >= 3 * LPT && DBG == 0;
+    constexpr bool SPREAD = C::KS == 2 && C::NW == 8 && STAGES == 2 && (TN * TM) >= 3 * LPT;
     if (SPREAD) {
         for (int kt = 0; kt < nkt; ++kt) {
             read_frags(stage, 1, wf1, af1);
@@ -587,15 +551,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
     }
 
     // ---- epilogue: lane holds acc for out[m = mw0 + im*16 + r][n = nw0 + in*16 + 4g .. +3]
-    if (DBG == 4) {                      // diagnostic: no epilogue stores (keep the accumulators live)
-        f32x4_t t = acc[0][0];
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int k = 0; k < TM; ++k) t += acc[i][k];
-        if (t[0] == 123.456f) reinterpret_cast<float*>(out)[0] = t[1] + t[2] + t[3];
-        return;
-    }
     const int nw0 = n0 + wn * WT_N;
     load_res_pass(0, rbuf[0]);
     __syncthreads();                     // every wave's last fragments are in registers: the ring is free
@@ -704,7 +659,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
                 if (ln_is_producer(LN) && OUT_F32)
                     ln_emit<DT>(__builtin_bit_cast(f32x4_t, d), ok,
                                 reinterpret_cast<unsigned short*>(ln.out16) + m * ln.ld16 + ep_col,
-                                ln.part_stats + ((int64_t)(ep_col >> 5) * ln.rows + m) * 2, lane, ln.x16_scale, true, true,
+                                ln.part_stats + ((int64_t)(ep_col >> 5) * ln.rows + m) * 2, lane, ln.x16_scale,
                                 (T16 && ln.t16_out) ? ln.t16_out + m * ln.ldt16 + ep_col : nullptr, ln.t16_scale);
                 if (ok && (!ln_is_producer(LN) || out != nullptr))
                     *reinterpret_cast<u32x4_t*>(reinterpret_cast<char*>(out) + (m * ldo + ep_col) * ES) = d;
@@ -712,10 +667,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
         }
     }
 }
-
-#ifdef VF_TUNING   // gemm_persist_kernel: persistent 128x128 form, measured without gain (DESIGN_HISTORY.md)
-#include "tuning/gemm_persist.inc"
-#endif
 
 // ======================================================================================================================
 // 256 x 256 x 64 tile, 8 waves, two wave groups running half a phase apart ("8-phase" schedule: 4 phases per K-tile,
@@ -756,10 +707,6 @@ struct Cfg8 {
     enum { WL = 0, AL = 1, WH = 2, AH = 3 };
 };
 
-#ifdef VF_G8_PROF
-__device__ unsigned long long* vf_g8_prof = nullptr;      // scripts/probes/gemm8_probe.hip: cycle stamps of every 16th block
-#endif
-
 template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __restrict__ A, int64_t lda,
                                                        const unsigned short* __restrict__ W,
@@ -773,24 +720,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
 
     // XCD-aware bijective remap + grouped order (same as gemm_mfma_kernel)
     const int bid = blockIdx.x;
-#ifdef VF_G8_PROF
-    unsigned long long g8t[8]; int g8n = 0;
-#define G8_MARK() { g8t[g8n < 8 ? g8n : 7] = __builtin_readcyclecounter(); ++g8n; }
-    G8_MARK()
-#else
-#define G8_MARK()
-#endif
-#ifdef VF_TUNING   // cost-centre probes of the epilogue (VF_G8_DBG bit mask, scripts/gemm_bench.py; results meaningless)
-    const int dbg = (GROUP_M >> 8) & 255;
-    // start-up stagger experiment (VF_G8_STAGGER = units of ~4 us): every other CU of an XCD starts its FIRST tile late, so
-    // that the epilogue bursts of the two halves do not coincide (later blocks inherit the phase of the CU they land on)
-    const int stagger = GROUP_M >> 16;
-    GROUP_M &= 255;
-    if (stagger && bid < 256 && ((bid >> 3) & 1))
-        for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
-#else
-    constexpr int dbg = 0;
-#endif
     const int q8 = n_blocks >> 3, r8 = n_blocks & 7, xcd = bid & 7, loc = bid >> 3;
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
     const int tiles_m = n_blocks / tiles_n;
@@ -916,7 +845,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    G8_MARK()                                        // 1: first K-tile in LDS
     if (wm == 1) __builtin_amdgcn_s_barrier();       // group 1 runs one barrier behind (matched after the loop)
 
     for (int t = 0; t < nkt; ++t) {
@@ -956,7 +884,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
     }
     if (wm == 0) __builtin_amdgcn_s_barrier();       // matches group 1's extra barrier: every wave is past its last MFMA
     asm volatile("" ::: "memory");
-    G8_MARK()                                        // 2: K loop done
 #undef VF_G8_SYNC_IN
 #undef VF_G8_SYNC_OUT
 #undef VF_G8_MMA
@@ -1012,11 +939,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
     float* part_run = part_p;
     unsigned short* t16_run = T16 ? ln.t16_out + row0 * ln.ldt16 + ep_col : nullptr;
     const int64_t t16_step = (int64_t)RI * ln.ldt16;
-    // VF_G8_RES_ALL (experiment, off): 16-bit residual rows of ALL passes requested up front (NPASS * NI items of 2 registers
-    // = 64 of the registers the operand fragments no longer need) instead of one pass ahead.
-    constexpr bool RES_ALL = R16 && RES && (VF_G8_RES_ALL != 0);
-    constexpr int NRB = RES_ALL ? NPASS : 2;
-    res_t rbuf[NRB][RES ? NI : 1];
+    res_t rbuf[2][RES ? NI : 1];
     auto load_res_pass = [&](int ps, res_t (&dst)[RES ? NI : 1]) {
         if (RES) {
 #pragma unroll
@@ -1024,7 +947,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
                 const int j = ps * NI + k;
                 const char* rp = (j * RI < rows_left) ? res_run : res_last;
                 res_run += res_step;
-                if (dbg & 8) { dst[RES ? k : 0] = res_t{}; continue; }
                 dst[RES ? k : 0] = *reinterpret_cast<const res_t*>(rp);
             }
         }
@@ -1038,10 +960,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
         else return v;
     };
     load_res_pass(0, rbuf[0]);
-    if (RES_ALL) {
-#pragma unroll
-        for (int ps = 1; ps < NPASS; ++ps) load_res_pass(ps, rbuf[ps < NRB ? ps : 0]);
-    }
     // bias of the wave's columns, from the side area (requested before the first K-tile)
     f32x4_t bvec[TN];
     if (bias) {
@@ -1082,7 +1000,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
     char* const region = smem + wave * REGION;
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
-        if (!RES_ALL && ps + 1 < NPASS) load_res_pass(ps + 1, rbuf[(ps + 1) & 1]);
+        if (ps + 1 < NPASS) load_res_pass(ps + 1, rbuf[(ps + 1) & 1]);
 #pragma unroll
         for (int iml = 0; iml < IMP; ++iml) {
             const int im = ps * IMP + iml;
@@ -1134,12 +1052,12 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
                 u32x4_t d = dd[k];
                 if (RES) {
                     f32x4_t f = __builtin_bit_cast(f32x4_t, d);
-                    f += res_value(rbuf[RES_ALL ? (ps < NRB ? ps : 0) : (ps & 1)][RES ? k0 + k : 0]);
+                    f += res_value(rbuf[ps & 1][RES ? k0 + k : 0]);
                     d = __builtin_bit_cast(u32x4_t, f);
                 }
                 const bool ok = j * RI + ep_row < WT_M && j * RI < rows_left && ep_col < n_out_total;
                 if (ln_is_producer(LN) && OUT_F32) {
-                    ln_emit<DT>(__builtin_bit_cast(f32x4_t, d), ok, o16_run, part_run, lane, ln.x16_scale, !(dbg & 2), !(dbg & 4),
+                    ln_emit<DT>(__builtin_bit_cast(f32x4_t, d), ok, o16_run, part_run, lane, ln.x16_scale,
                                 (T16 && ln.t16_out) ? t16_run : nullptr, ln.t16_scale);
                     o16_run += o16_step;
                     part_run += RI * 2;
@@ -1147,19 +1065,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
                 }
                 // a LayerNorm producer whose fp32 result has no reader (only its 16-bit copy and statistics do) passes
                 // out = NULL: the 16-byte store -- 4 of the 10 bytes the epilogue moves per element -- is dropped
-                if (ok && (!ln_is_producer(LN) || out != nullptr) && !(dbg & 1)) *reinterpret_cast<u32x4_t*>(out_run) = d;
+                if (ok && (!ln_is_producer(LN) || out != nullptr)) *reinterpret_cast<u32x4_t*>(out_run) = d;
                 out_run += out_step;
             }
         }
-        G8_MARK()                                    // 3 .. 6: epilogue passes
     }
-#ifdef VF_G8_PROF
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    G8_MARK()                                        // 7: stores acknowledged
-    if (vf_g8_prof && lane == 0 && wave == 0 && (bid & 15) == 0)
-        for (int i = 0; i < 8; ++i) vf_g8_prof[(bid >> 4) * 8 + i] = g8t[i];
-#endif
-#undef G8_MARK
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
@@ -1185,12 +1095,6 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
 
     // XCD-aware bijective remap + grouped order (same as gemm_mfma_kernel)
     const int bid = blockIdx.x;
-#ifdef VF_TUNING   // cost-centre probes of the epilogue (VF_G8_DBG bit mask, scripts/gemm_bench.py; results meaningless)
-    const int dbg = GROUP_M >> 8;
-    GROUP_M &= 255;
-#else
-    constexpr int dbg = 0;
-#endif
     const int grid = gridDim.x;
     const int my_tiles = (n_tiles - bid + grid - 1) / grid;          // output tiles bid, bid + grid, ... (>= 1)
     auto tile_origin = [&](int t, int& m0, int& n0) {                 // XCD-contiguous runs, grouped order (see gemm_mfma_kernel)
@@ -1231,9 +1135,6 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
     // half-tile `type` of the K-tile with index kt inside the tile `src` points at; gk = its index in the block's
     // K-tile stream (the ring buffer is the stream index's parity, so the stream runs across output tiles)
     auto issue = [&](int gk, int kt, int type) {
-#ifdef VF_G8X_NOFILL      // probe build: the K loop without its LDS-DMA stream (stale LDS contents; results meaningless)
-        if (gk > 1) return;
-#endif
         char* dst = lds_piece + (gk & 1) * C::TILE_BYTES + type * C::HALF_BYTES;
         glds16(src[type][0] + kt * BK, dst);
         glds16(src[type][1] + kt * BK, dst + 1024);
@@ -1314,44 +1215,6 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
                         Op16<DT>::mfma(WF[i][ks], af[j][ks], acc[IN0 + i][IM0 + j]); \
     } while (0)
 
-    // Probe (tuning library only, VF_G8_DBG bits 16 / 32; results meaningless): one / two 16-byte-per-lane stores per phase
-    // into the rows of the CURRENT tile (16 rows x 64 bytes per instruction, the shape of an epilogue without LDS staging),
-    // issued in the fragment-read section -- do stores beside the LDS-DMA stream cost the K loop anything?  (round 6: the
-    // question behind an epilogue inside the K loop; 32 / 64 KiB per K-tile and block against 64 KiB of fill.)
-#ifdef VF_TUNING
-#define VF_G8X_STORE_PROBE(PH)                                                                                         \
-    do {                                                                                                               \
-        /* bits 64 / 128: the store pattern of an epilogue inside the K loop -- 4 stores (32 rows x 64 columns of 16-bit */ \
-        /* values) in P1 and P2 of a tile's first K-tile (64: they get 1.75 / 1.5 K-tiles until a counted wait needs them */ \
-        /* complete), or in P3 and behind the wait of P4 of its second K-tile (128: 1.25 / 1 K-tiles) */               \
-        if (((dbg & 64) && (PH) < 2 && t == 0 && ti > 0) || ((dbg & 128) && (PH) >= 2 && t == 1)) {                    \
-            int lp;                                                                                                    \
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lp));                   \
-            const int prow = m0 + wm * 128 + ((PH) >> 1) * 64 + ((PH) & 1) * 32 + (lp & 15);                            \
-            const int pcol = n0 + wn * 64 + (lp >> 4) * 8;                                                             \
-            if (prow + 16 < M && pcol + 32 < N) {                                                                      \
-                unsigned short* pp = reinterpret_cast<unsigned short*>(out) + (int64_t)prow * ldo + pcol;              \
-                *reinterpret_cast<f32x4_t*>(pp) = acc[0][0];                                                           \
-                *reinterpret_cast<f32x4_t*>(pp + 32) = acc[0][1];                                                      \
-                *reinterpret_cast<f32x4_t*>(pp + 16 * ldo) = acc[1][0];                                                \
-                *reinterpret_cast<f32x4_t*>(pp + 16 * ldo + 32) = acc[1][1];                                           \
-            }                                                                                                          \
-        }                                                                                                              \
-        if (dbg & 48) {                                                                                                \
-            int lp;                                                                                                    \
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lp));                   \
-            const int prow = m0 + wm * 128 + (((t * 4 + (PH)) * 16 + (lp & 15)) & 127);                                \
-            const int pcol = n0 + wn * 64 + (lp >> 4) * 8;                                                             \
-            if (prow < M && pcol + 32 < N) {                                                                           \
-                unsigned short* pp = reinterpret_cast<unsigned short*>(out) + (int64_t)prow * ldo + pcol;              \
-                *reinterpret_cast<f32x4_t*>(pp) = acc[0][0];                                                           \
-                if (dbg & 32) *reinterpret_cast<f32x4_t*>(pp + 32) = acc[0][1];                                        \
-            }                                                                                                          \
-        }                                                                                                              \
-    } while (0)
-#else
-#define VF_G8X_STORE_PROBE(PH) do { } while (0)
-#endif
     // ---- first tile: its epilogue operands and K-tile 0
     const int nkt = K / BK;                                  // >= 2 (launcher)
     int m0, n0;
@@ -1361,17 +1224,9 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
     issue(0, 0, C::WL); issue(0, 0, C::AL); issue(0, 0, C::WH); issue(0, 0, C::AH);
 
     int g0 = 0;                                              // stream index of the current tile's K-tile 0
-#ifdef VF_G8_PROF   // scripts/probes/gemm8x_probe.hip: per block, cycles summed over its tiles (wave 0 = group 0, wave 4 = group 1)
-    unsigned long long px[6] = {0, 0, 0, 0, 0, 0}, pt0, pt1;
-#define G8X_T() __builtin_readcyclecounter()
-    const unsigned long long pc0 = __builtin_amdgcn_s_memtime(), pr0 = __builtin_amdgcn_s_memrealtime();   // clock held under load:
-#endif                                                                                                    // d(memtime) / d(memrealtime) x 100 MHz
     for (int ti = 0; ti < my_tiles; ++ti) {
         const bool has_next = ti + 1 < my_tiles;             // block-uniform
         tile_origin(bid + ti * grid, m0, n0);
-#ifdef VF_G8_PROF
-        pt0 = G8X_T();
-#endif
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
@@ -1384,14 +1239,8 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (wm == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind (matched after the loop)
-#ifdef VF_G8_PROF
-        pt1 = G8X_T(); px[0] += pt1 - pt0; pt0 = pt1;        // 0: tile start (K-tile 1 requested, start barriers)
-#endif
 
         for (int t = 0; t < nkt; ++t) {
-#ifdef VF_G8_PROF
-            if (t == 1) { pt1 = G8X_T(); px[1] += pt1 - pt0; pt0 = pt1; }      // 1: the first K-tile of the tile
-#endif
             const char* buf = smem + ((g0 + t) & 1) * C::TILE_BYTES;
             // the stream continues into the NEXT output tile for exactly one K-tile: its K-tile 0 is "K-tile nkt"
             const bool pre1 = t + 1 < nkt || has_next;                       // AH of stream K-tile t+1
@@ -1403,7 +1252,6 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
             read_a(buf, C::AL);
             if (pre1) issue(g0 + t + 1, t + 1 < nkt ? t + 1 : 0, C::AH);
             asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");       // ... and retired before the barrier (WAR on WL)
-            VF_G8X_STORE_PROBE(0);
             VF_G8_SYNC_IN();
             VF_G8_MMA(wlo, 0, 0);
             VF_G8_SYNC_OUT();
@@ -1416,41 +1264,28 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
             // ---- P2: (m-lo, n-hi)
             read_w(buf, C::WH, whi);
             if (pre2) issue(g0 + t + 2, into_next ? 0 : t + 2, C::WL);
-            VF_G8X_STORE_PROBE(1);
             VF_G8_SYNC_IN();
             VF_G8_MMA(whi, 2, 0);
             VF_G8_SYNC_OUT();
             // ---- P3: (m-hi, n-hi)
             read_a(buf, C::AH);
             if (pre2) issue(g0 + t + 2, into_next ? 0 : t + 2, C::AL);
-            VF_G8X_STORE_PROBE(2);
             VF_G8_SYNC_IN();
             VF_G8_MMA(whi, 2, 4);
             VF_G8_SYNC_OUT();
             // ---- P4: (m-hi, n-lo); retire stream K-tile t+1 (all but the three youngest half-tiles)
             if (pre2) {
                 issue(g0 + t + 2, into_next ? 0 : t + 2, C::WH);
-#ifdef VF_TUNING
-                if (dbg & 32) wait_vmcnt<12>();                      // store probe: its stores since AH(t + 1) may stay in flight too
-                else if (dbg & 16) wait_vmcnt<9>();
-                else if ((dbg & 64) && t == 0 && ti > 0) wait_vmcnt<14>();
-                else if ((dbg & 128) && t == 1) wait_vmcnt<10>();
-                else
-#endif
                 wait_vmcnt<6>();
             } else {
                 wait_vmcnt<0>();
             }
-            VF_G8X_STORE_PROBE(3);
             VF_G8_SYNC_IN();
             VF_G8_MMA(wlo, 0, 4);
             VF_G8_SYNC_OUT();
         }
         if (wm == 0) __builtin_amdgcn_s_barrier();   // matches group 1's extra barrier: every wave is past its last MFMA
         asm volatile("" ::: "memory");
-#ifdef VF_G8_PROF
-        pt1 = G8X_T(); px[2] += pt1 - pt0; pt0 = pt1;        // 2: K-tiles 1 .. nkt-1 (+ the group-sync barrier)
-#endif
         char* const side = smem + C::LDS_BYTES + C::SPARE_BYTES + (ti & 1) * C::SIDE_BYTES;
         // Staging: the last K-tile's buffer is free now (the other one holds, or is receiving, the next tile's K-tile 0).
         // K / 64 is even (launcher), so that is always buffer 1, and the 24 KiB of LDS that lie unused behind the ring
@@ -1464,7 +1299,7 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
         const int lane = lane_e, r = lane & 15, g = lane >> 4;
 
         // 16-bit-residual LayerNorm producers: the wide read-back form (producer16_epilogue_wide above)
-        constexpr bool WIDE = ln_res_is_16(LN) && EPI == VF_EPI_RES_F32 && (VF_G8X_WIDE != 0);
+        constexpr bool WIDE = ln_res_is_16(LN) && EPI == VF_EPI_RES_F32;
         if constexpr (WIDE) {
             producer16_epilogue_wide<DT, LN, (C::TILE_BYTES + C::SPARE_BYTES) / C::NW>(
                 acc, stage_buf + wave * ((C::TILE_BYTES + C::SPARE_BYTES) / C::NW), side, wn * 64, (int64_t)m0 + wm * 128,
@@ -1530,7 +1365,6 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
                     const int j = ps * NI + k;
                     const char* rp = (j * RI < rows_left) ? res_run : res_last;
                     res_run += res_step;
-                    if (dbg & 8) { dst[RES ? k : 0] = res_t{}; continue; }
                     dst[RES ? k : 0] = *reinterpret_cast<const res_t*>(rp);
                 }
             }
@@ -1636,7 +1470,7 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
                     }
                     const bool ok = j * RI + ep_row < WT_M && j * RI < rows_left && ep_col < n_out_total;
                     if (ln_is_producer(LN) && OUT_F32) {
-                        ln_emit<DT>(__builtin_bit_cast(f32x4_t, d), ok, o16_run, part_run, lane, ln.x16_scale, !(dbg & 2), !(dbg & 4),
+                        ln_emit<DT>(__builtin_bit_cast(f32x4_t, d), ok, o16_run, part_run, lane, ln.x16_scale,
                                     (T16 && ln.t16_out) ? t16_run : nullptr, ln.t16_scale);
                         o16_run += o16_step;
                         part_run += RI * 2;
@@ -1644,7 +1478,7 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
                     }
                     // a LayerNorm producer whose fp32 result has no reader (only its 16-bit copy and statistics do) passes
                     // out = NULL: the 16-byte store -- 4 of the 10 bytes the epilogue moves per element -- is dropped
-                    if (ok && (!ln_is_producer(LN) || out != nullptr) && !(dbg & 1)) *reinterpret_cast<u32x4_t*>(out_run) = d;
+                    if (ok && (!ln_is_producer(LN) || out != nullptr)) *reinterpret_cast<u32x4_t*>(out_run) = d;
                     out_run += out_step;
                 }
             }
@@ -1653,41 +1487,14 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
         }   // !WIDE
 
         // every wave's staging reads are done before the next tile's K-tile 1 is requested into this buffer
-#ifdef VF_G8_PROF
-        pt1 = G8X_T(); px[3] += pt1 - pt0; pt0 = pt1;        // 3: epilogue passes of this wave
-#endif
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-#ifdef VF_G8_PROF
-        pt1 = G8X_T(); px[4] += pt1 - pt0; px[5] += 1;       // 4: waiting for the other waves' epilogues
-#endif
         g0 += nkt;
     }
-#ifdef VF_G8_PROF
-    if (vf_g8_prof && (tid & 63) == 0 && (wave == 0 || wave == 4) && (bid & 7) == 0) {
-        for (int i = 0; i < 6; ++i) vf_g8_prof[((bid >> 3) * 2 + (wave >> 2)) * 8 + i] = px[i];
-        vf_g8_prof[((bid >> 3) * 2 + (wave >> 2)) * 8 + 6] = __builtin_amdgcn_s_memtime() - pc0;
-        vf_g8_prof[((bid >> 3) * 2 + (wave >> 2)) * 8 + 7] = __builtin_amdgcn_s_memrealtime() - pr0;
-    }
-#undef G8X_T
-#endif
 #undef VF_G8_SYNC_IN
 #undef VF_G8_SYNC_OUT
 #undef VF_G8_MMA
-#undef VF_G8X_STORE_PROBE
 }
-
-#ifdef VF_TUNING   // gemm8y_kernel: the epilogue inside the K loop -- ruled out by the store probe before it ran (profiles/r06_b)
-#include "tuning/gemm8y.inc"
-#endif
-
-#ifdef VF_TUNING   // gemm4_kernel: two independent 4-wave blocks per CU, 15-20 % slower (profiles/r04_a)
-#include "tuning/gemm4.inc"
-#endif
-
-#ifdef VF_TUNING   // gemm8p_kernel: prefetch-all variant of the two-group kernel, mixed results (DESIGN_HISTORY.md)
-#include "tuning/gemm8p.inc"
-#endif
 
 // Shape-generic fallback (any K % 8 == 0): 64x64 tile, fp32 FMA out of LDS.  Same lane->output
 // ownership as the MFMA kernel so the epilogues are shared.  Only small/odd shapes come here.
@@ -1745,29 +1552,15 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(const unsigned short*
     }
 }
 
-#ifdef VF_TUNING   // xs_gemm_kernel: projection phase of a fused seq2reg block, 5-7 % slower (profiles/r03_e)
-#include "tuning/gemm_xs.inc"
-#endif
-
 // The product library instantiates only the configurations pick_variant() can select.
 using CfgA = Cfg<128, 128, 2, 2, 2>;       // 64 KiB, 4 waves, 2 blocks/CU
 using CfgE = Cfg<64, 64, 2, 2, 4>;         // 64 KiB, small-M shapes, 2 blocks/CU
-#ifdef VF_TUNING                            // tile sweep of scripts/gemm_bench.py (all measured equal or slower)
-using CfgB = Cfg<256, 256, 2, 4, 2>;       // 128 KiB, 8 waves, wave tile 128x64, one barrier per K-tile (round 1's big tile)
-using CfgJ = Cfg<128, 128, 2, 2, 3, 32>;   // 48 KiB, 4 waves, BK=32, 2 tiles in flight, 3 blocks/CU
-using CfgC = Cfg<256, 128, 4, 2, 3>;       // 144 KiB, 8 waves, wave tile 64x64, 2 tiles in flight
-using CfgD = Cfg<256, 256, 2, 4, 4, 32>;   // 128 KiB, 8 waves, BK=32, 3 tiles in flight
-using CfgF = Cfg<128, 256, 2, 4, 3>;       // 144 KiB, 8 waves, wave tile 64x64
-using CfgG = Cfg<128, 128, 2, 2, 4, 32>;   // 64 KiB, 4 waves, BK=32, 3 tiles in flight, 2 blocks/CU
-using CfgH = Cfg<256, 128, 2, 2, 3, 32>;   // 72 KiB, 4 waves (wave tile 128x64), BK=32, 2 blocks/CU
-using CfgI = Cfg<128, 256, 2, 2, 3, 32>;   // 72 KiB, 4 waves (wave tile 64x128), BK=32, 2 blocks/CU
-#endif
 
-template <class C, int EPI, int DT = VF_BF16, int DBG = 0, int LN = VF_LN_NONE>
+template <class C, int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
 int launch_cfg(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
                int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
     static bool attr_set[VF_MAX_DEVICES] = {};    // per (config, epilogue) instantiation AND per device
-    auto kern = gemm_mfma_kernel<C, EPI, DT, DBG, LN>;
+    auto kern = gemm_mfma_kernel<C, EPI, DT, LN>;
     const int dev = vf_current_device();
     if (dev < 0 || !attr_set[dev]) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1788,33 +1581,6 @@ int launch_cfg(const void* A, int64_t lda, const void* W, const float* bias, con
     return VF_OK;
 }
 
-#ifdef VF_TUNING
-template <class C, int EPI, int DT = VF_BF16>
-int launch_persist(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
-                   int64_t ldo, int M, int N, int K, hipStream_t st) {
-    static bool attr_set = false;
-    auto kern = gemm_persist_kernel<C, EPI, DT>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                C::LDS_BYTES) != hipSuccess) {
-            (void)hipGetLastError();
-            vf_set_error("vf_gemm_bf16: cannot reserve %d bytes of LDS", C::LDS_BYTES);
-            return VF_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
-    const int tiles_m = (M + C::BM - 1) / C::BM, tiles_n = (N + C::BN - 1) / C::BN;
-    const int n_tiles = tiles_m * tiles_n;
-    const int slots = 256 * (163840 / C::LDS_BYTES >= 2 ? 2 : 1);      // resident blocks: CUs x blocks per CU by LDS
-    const int grid = n_tiles < slots ? n_tiles : slots;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, st, (const unsigned short*)A, lda,
-                       (const unsigned short*)W, bias, res, ldr, out, ldo, M, N, K, tiles_n, n_tiles);
-    VF_CHECK_LAUNCH("vf_gemm_bf16");
-    return VF_OK;
-}
-
-#endif  // VF_TUNING
-
 template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
 int launch_gemm8(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
                  int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
@@ -1832,12 +1598,7 @@ int launch_gemm8(const void* A, int64_t lda, const void* W, const float* bias, c
     }
     const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
     const int n_blocks = tiles_m * tiles_n;
-    int group_m = 8;
-#ifdef VF_TUNING
-    if (const char* e = getenv("VF_G8_GROUP_M")) group_m = atoi(e);     // tile-walk sweep (scripts/gemm_bench.py)
-    if (const char* e = getenv("VF_G8_DBG")) group_m |= atoi(e) << 8;   // epilogue cost-centre probes
-    if (const char* e = getenv("VF_G8_STAGGER")) group_m |= atoi(e) << 16;
-#endif
+    const int group_m = 8;
     vf_note_kernel(0, "gemm8_kernel");
     hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(512), Cfg8::LDS_BYTES + Cfg8::SIDE_BYTES, st, (const unsigned short*)A, lda,
                        (const unsigned short*)W, bias, res, ldr, out, ldo, M, N, K, tiles_n, n_blocks, group_m, ln);
@@ -1874,11 +1635,7 @@ int launch_gemm8x(const void* A, int64_t lda, const void* W, const float* bias, 
     const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
     const int n_tiles = tiles_m * tiles_n;
     const int grid = n_tiles < cus ? n_tiles : cus;              // one resident block per CU
-    int group_m = 8;
-#ifdef VF_TUNING
-    if (const char* e = getenv("VF_G8X_GROUP_M")) group_m = atoi(e);    // tile-walk sweep (scripts/gemm4_probe.py)
-    if (const char* e = getenv("VF_G8_DBG")) group_m |= atoi(e) << 8;   // epilogue cost-centre probes
-#endif
+    const int group_m = 8;
     vf_note_kernel(0, "gemm8x_kernel");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, (const unsigned short*)A, lda, (const unsigned short*)W, bias,
                        res, ldr, out, ldo, M, N, K, tiles_n, n_tiles, group_m, ln);
@@ -1886,88 +1643,11 @@ int launch_gemm8x(const void* A, int64_t lda, const void* W, const float* bias, 
     return VF_OK;
 }
 
-#ifdef VF_TUNING
-template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
-int launch_gemm4(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
-                 int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
-    constexpr int LDS = Cfg4::LDS_BYTES;                         // 80 KiB: two blocks per CU
-    static bool attr_set[VF_MAX_DEVICES] = {};
-    static int n_cu[VF_MAX_DEVICES] = {};
-    auto kern = gemm4_kernel<EPI, DT, LN>;
-    const int dev = vf_current_device();
-    if (dev < 0 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) !=
-            hipSuccess) {
-            (void)hipGetLastError();
-            vf_set_error("vf_gemm: cannot reserve %d bytes of LDS", LDS);
-            return VF_ERR_LAUNCH;
-        }
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    int cus = 256;
-    if (dev >= 0) {
-        if (n_cu[dev] == 0) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-            n_cu[dev] = v;
-        }
-        cus = n_cu[dev];
-    }
-    const int tiles_m = (M + Cfg4::BM - 1) / Cfg4::BM, tiles_n = (N + Cfg4::BN - 1) / Cfg4::BN;
-    const int n_tiles = tiles_m * tiles_n;
-    int slots = 2 * cus;                                         // two resident blocks per CU
-    int lds = LDS;
-    int group_m = 8;
-#ifdef VF_TUNING
-    if (const char* e = getenv("VF_G4_GROUP_M")) group_m = atoi(e);
-    if (const char* e = getenv("VF_G4_STAGGER")) group_m |= atoi(e) << 16;
-    if (const char* e = getenv("VF_G4_BPC")) slots = atoi(e) * cus;      // residency probes: blocks per CU, LDS request
-    if (const char* e = getenv("VF_G4_LDS")) {
-        lds = atoi(e);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    }
-#endif
-    const int grid = n_tiles < slots ? n_tiles : slots;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, (const unsigned short*)A, lda, (const unsigned short*)W, bias,
-                       res, ldr, out, ldo, M, N, K, tiles_n, n_tiles, group_m, ln);
-    VF_CHECK_LAUNCH("vf_gemm");
-    return VF_OK;
-}
-#endif  // VF_TUNING
-
-#ifdef VF_TUNING
-template <int EPI, int DT = VF_BF16>
-int launch_gemm8p(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
-                  int64_t ldo, int M, int N, int K, hipStream_t st) {
-    constexpr int LDS = Cfg8::LDS_BYTES + 8 * 4096;              // ring + per-wave epilogue scratch = 160 KiB
-    static bool attr_set[VF_MAX_DEVICES] = {};
-    auto kern = gemm8p_kernel<EPI, DT>;
-    const int dev = vf_current_device();
-    if (dev < 0 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) !=
-            hipSuccess) {
-            (void)hipGetLastError();
-            vf_set_error("vf_gemm: cannot reserve %d bytes of LDS", LDS);
-            return VF_ERR_LAUNCH;
-        }
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
-    const int n_tiles = tiles_m * tiles_n;
-    const int grid = n_tiles < 256 ? n_tiles : 256;              // one resident block per CU
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, (const unsigned short*)A, lda, (const unsigned short*)W, bias,
-                       res, ldr, out, ldo, M, N, K, tiles_n, n_tiles, 8);
-    VF_CHECK_LAUNCH("vf_gemm");
-    return VF_OK;
-}
-
-#endif  // VF_TUNING
-
 // Tile choice (measured on MI355X, scripts/gemm_bench.py, random data; the cost model inside reproduces every measured
 // ordering): grids with fewer than 256 128x128 tiles use 64x64 tiles so that all 256 CUs get work; otherwise 256x256
 // (one 8-wave block per CU, half the L2 -> LDS bytes per flop) against 128x128 (two 4-wave blocks per CU) by whole
 // waves of tiles.
-// variant 0 = automatic; 1 / 5 / 20 / 22 force a configuration (tests).  Other numbers exist only under VF_TUNING.
+// variant 0 = automatic; 1 / 5 / 20 / 22 force a configuration (tests).
 int pick_variant(int M, int N, int K, int epilogue) {
     const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
@@ -1985,21 +1665,10 @@ int pick_variant(int M, int N, int K, int epilogue) {
     // 16-bit epilogues take the persistent form of the 256x256 kernel (first fill and block launch hidden: seq2reg Wqkv
     // 890 -> 953, GeGLU 893 -> 976, gene Wqkv / Wq / GeGLU +2-3 %, same box).  The fp32 epilogues stay on the one-shot
     // kernel: staged through half the ring (16-row passes) the seq2reg N = 512 producers lose 8 %, the gene ones gain
-    // nothing.  VF_GEMM_PERSIST=0 switches the persistent form off (A/B runs).
-    static const int persist = vf_tuning_env("VF_GEMM_PERSIST", 1);
+    // nothing.
     const bool out16 = epilogue == VF_EPI_BF16 || epilogue == VF_EPI_GEGLU_BF16 || epilogue == VF_EPI_GELU_BF16;
-    return (persist && (out16 || persist >= 2) && K % 128 == 0) ? 22 : 20;      // K / 64 even: see the kernel's staging
+    return (out16 && K % 128 == 0) ? 22 : 20;      // K / 64 even: see the kernel's staging
 }
-
-#ifdef VF_TUNING
-// Variant 23 = gemm8y_kernel (tuning library only, VF_GEMM8Y=1): the epilogue inside the K loop.  Never validated on hardware:
-// the store probe of gemm8x_kernel (VF_G8_DBG bits 64 / 128) showed that its 16 in-loop stores per wave and tile cost as much as
-// the serial epilogue they would replace, and the kernel spills 28-83 registers.
-static inline bool gemm8y_ok(int K, int epilogue) {
-    static const int on = vf_tuning_env("VF_GEMM8Y", 0);
-    return on && K % 128 == 0 && K >= 256 && (epilogue == VF_EPI_BF16 || epilogue == VF_EPI_GEGLU_BF16);
-}
-#endif
 
 template <int EPI, int DT>
 int launch_gemm(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
@@ -2012,57 +1681,13 @@ int launch_gemm(const void* A, int64_t lda, const void* W, const float* bias, co
         VF_CHECK_LAUNCH("vf_gemm_bf16");
         return VF_OK;
     }
-    if (variant == 0) {
-        variant = pick_variant(M, N, K, EPI);
-#ifdef VF_TUNING
-        if (variant == 22 && gemm8y_ok(K, EPI)) variant = 23;
-#endif
-    }
+    if (variant == 0) variant = pick_variant(M, N, K, EPI);
     switch (variant) {
-#ifdef VF_TUNING
-        case 23:
-            if constexpr (EPI == VF_EPI_BF16 || EPI == VF_EPI_GEGLU_BF16) {
-                if (K % 128 == 0 && K >= 256) return launch_gemm8y<EPI, DT>(A, lda, W, bias, out, ldo, M, N, K, st);
-            }
-            break;
-#endif
         case 1: return launch_cfg<CfgA, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
         case 5: return launch_cfg<CfgE, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
         case 20: return launch_gemm8<EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
         case 22: if (K % 128 == 0) return launch_gemm8x<EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
                  return launch_gemm8<EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-#ifdef VF_TUNING
-        case 30:
-            if constexpr (EPI == VF_EPI_BF16 || EPI == VF_EPI_GEGLU_BF16) {
-                if (xs_ok(N, K, EPI)) return launch_xs<EPI, DT, VF_LN_NONE>(A, lda, W, bias, out, ldo, M, N, st);
-            }
-            break;
-        case 40: if (K % 128 == 0) return launch_gemm4<EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-                 return launch_gemm8<EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 21:
-            if (K < 128) break;
-            return launch_gemm8p<EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 2: return launch_cfg<CfgB, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 12: return launch_cfg<CfgJ, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 3: return launch_cfg<CfgC, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 4: return launch_cfg<CfgD, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 6: return launch_cfg<CfgF, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 7: return launch_cfg<CfgG, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 8: return launch_cfg<CfgH, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 9: return launch_cfg<CfgI, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 104: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgA, VF_EPI_BF16, VF_BF16, 4>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 103: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgA, VF_EPI_BF16, VF_BF16, 3>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 204: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgB, VF_EPI_BF16, VF_BF16, 4>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 203: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgB, VF_EPI_BF16, VF_BF16, 3>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 101: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgA, VF_EPI_BF16, VF_BF16, 1>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 102: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgA, VF_EPI_BF16, VF_BF16, 2>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 201: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgB, VF_EPI_BF16, VF_BF16, 1>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 202: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgB, VF_EPI_BF16, VF_BF16, 2>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 401: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgD, VF_EPI_BF16, VF_BF16, 1>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 402: if (EPI == VF_EPI_BF16 && DT == VF_BF16) return launch_cfg<CfgD, VF_EPI_BF16, VF_BF16, 2>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st); break;
-        case 10: return launch_persist<CfgA, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-        case 11: return launch_persist<CfgE, EPI, DT>(A, lda, W, bias, res, ldr, out, ldo, M, N, K, st);
-#endif  // VF_TUNING
         default: break;
     }
     vf_set_error("vf_gemm_bf16_ex: unknown variant %d", variant);
@@ -2116,48 +1741,18 @@ static int gemm_dispatch(const void* A, int64_t lda, const void* W, const float*
 template <int EPI, int DT, int LN>
 static int launch_gemm_ln(const void* A, int64_t lda, const void* W, const float* bias, const float* residual, int64_t ldr,
                           void* out, int64_t ldo, int M, int N, int K, const LnArgs& ln, hipStream_t st) {
-#ifdef VF_TUNING
-    if constexpr (LN == VF_LN_CONSUMER) {
-        // A/B switch (off by default: measured 906-942 against 955-1009 TFLOP/s for the persistent tile kernel on the
-        // seq2reg shapes, profiles/r03_e_xs_gemm.log): 1 = grids of >= 256 blocks, 2 = every K = 512 consumer (tests)
-        static const int xs = vf_tuning_env("VF_GEMM_XS", 0);
-        if (xs && xs_ok(N, K, EPI) && (xs >= 2 || M >= 256 * 256))
-            return launch_xs<EPI, DT, LN>(A, lda, W, bias, out, ldo, M, N, st, ln);
-    }
-#endif
     int variant = pick_variant(M, N, K, EPI);
-    if constexpr (LN == VF_LN_PRODUCER_T16) {
-        // the fp16-trunk down-projection: persistent form when no fp32 rows are stored (VF_GEMM_PERSIST_T16, default on: gene down-projection 829 -> 857, seq2reg 858 -> 897 TFLOP/s)
-        static const int pt16 = vf_tuning_env("VF_GEMM_PERSIST_T16", 1);
-        if (variant == 20 && K % 128 == 0 && pt16 && out == nullptr) variant = 22;
-    }
-    if constexpr (LN == VF_LN_PRODUCER_R16) {
+    if constexpr (ln_res_is_16(LN)) {
         // A producer whose residual is a 16-bit stream copy fits the persistent form with the one-shot kernel's 32-row
-        // passes (half the residual registers of the fp32 one): first fill and block hand-over hidden, gene out-projection
-        // 428-439 -> 408-414 us, seq2reg out-projection 662-675 -> 621-636 us (profiles/r03_v_persist_r16_ab.log).
-        // VF_GEMM_PERSIST_R16 = 1 (default): when no fp32 rows are stored either (the attention out-projections),
-        // 2: every such producer, 0: never.
-        static const int pr16 = vf_tuning_env("VF_GEMM_PERSIST_R16", 1);
-        if (variant == 20 && K % 128 == 0 && (pr16 >= 2 || (pr16 == 1 && out == nullptr))) variant = 22;
+        // passes (half the residual registers of the fp32 one) when no fp32 rows are stored: first fill and block hand-over
+        // hidden.  The attention out-projections (R16): gene 428-439 -> 408-414 us, seq2reg 662-675 -> 621-636 us
+        // (profiles/r03_v_persist_r16_ab.log); the fp16-trunk down-projection (T16): gene 829 -> 857, seq2reg 858 -> 897
+        // TFLOP/s.
+        if (variant == 20 && K % 128 == 0 && out == nullptr) variant = 22;
     }
-#ifdef VF_TUNING
-    {
-        // two 4-wave blocks per CU (gemm4_kernel) instead of the 8-wave 256x256 kernels: VF_GEMM4 bit mask, 1 = consumers,
-        // 2 = 16-bit-residual producers (R16 / T16), 4 = fp32-residual / plain producers
-        static const int g4 = getenv("VF_GEMM4") ? atoi(getenv("VF_GEMM4")) : 0;
-        const int bit = LN == VF_LN_CONSUMER ? 1 : (ln_res_is_16(LN) ? 2 : 4);
-        if ((variant == 20 || variant == 22) && K % 128 == 0 && (g4 & bit))
-            return launch_gemm4<EPI, DT, LN>(A, lda, W, bias, residual, ldr, out, ldo, M, N, K, st, ln);
-    }
-#endif
-#ifdef VF_TUNING
-    if constexpr (LN == VF_LN_CONSUMER && (EPI == VF_EPI_BF16 || EPI == VF_EPI_GEGLU_BF16)) {
-        if (variant == 22 && gemm8y_ok(K, EPI)) return launch_gemm8y<EPI, DT, LN>(A, lda, W, bias, out, ldo, M, N, K, st, ln);
-    }
-#endif
     switch (variant) {
-        case 1: return launch_cfg<CfgA, EPI, DT, 0, LN>(A, lda, W, bias, residual, ldr, out, ldo, M, N, K, st, ln);
-        case 5: return launch_cfg<CfgE, EPI, DT, 0, LN>(A, lda, W, bias, residual, ldr, out, ldo, M, N, K, st, ln);
+        case 1: return launch_cfg<CfgA, EPI, DT, LN>(A, lda, W, bias, residual, ldr, out, ldo, M, N, K, st, ln);
+        case 5: return launch_cfg<CfgE, EPI, DT, LN>(A, lda, W, bias, residual, ldr, out, ldo, M, N, K, st, ln);
         case 22: return launch_gemm8x<EPI, DT, LN>(A, lda, W, bias, residual, ldr, out, ldo, M, N, K, st, ln);
         default: return launch_gemm8<EPI, DT, LN>(A, lda, W, bias, residual, ldr, out, ldo, M, N, K, st, ln);
     }
