@@ -24,7 +24,7 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from variantformer_amd import ops  # noqa: E402
 from variantformer_amd.seq2gene.model_combined_modulator import Seq2GenePredictorCombinedModulator  # noqa: E402
-from variantformer_amd.seq2reg.model import Seq2RegPredictor  # noqa: E402
+from variantformer_amd.seq2reg.model import _LAYER0_SLOTS, Seq2RegPredictor  # noqa: E402
 from variantformer_amd.utils.synthetic import TISSUES_54, make_batch  # noqa: E402
 
 out_path = next((a for a in sys.argv[1:] if not a.startswith("--")), "gpurun_out/s2r_dims.json")
@@ -136,7 +136,7 @@ for d in widths:
                "seq2reg_attn_TFLOPs": round(attn["flops"] / max(attn["total_ms"], 1e-9) / 1e9, 1),
                "seq2reg_other_ms": round(other, 2), "kernels": kernels, "attention_launch_forms": attn_geoms,
                "layer0_table_bytes": int(cre_tok._layer0_qkv_table_bytes()),
-               "layer0_lookup_used": bool(getattr(cre_tok, "_qkv_tabs", None))})
+               "layer0_lookup_used": any(s in cre_tok.__dict__ for s in _LAYER0_SLOTS.values())})
         rows.append(rec)
         print(f"d={d:4d} h={heads:2d} dh={d // heads:3d} L={layers:2d} {pos[:4]} {pool:4s} ctx={int(ctx)}  {rec['genes_per_s']:7.2f} genes/s  "
               f"gemm {rec['seq2reg_gemm_ms']:7.2f} ms {rec['seq2reg_gemm_TFLOPs']:6.0f} TF/s  attn {rec['seq2reg_attn_ms']:6.2f} ms "

@@ -73,13 +73,17 @@ def test_gemm_beside_attention_on_another_stream_is_bit_identical(setup, victim,
                 assert torch.equal(o, coref)
 
 
-def test_two_models_in_two_threads_on_their_own_streams():
+@pytest.mark.parametrize("precisions", [("bf16-mixed", "bf16-mixed"), ("bf16-mixed", "16-mixed")], ids=["bf16_bf16", "bf16_fp16"])
+def test_two_models_in_two_threads_on_their_own_streams(precisions):
     """Two model instances driven from two threads, each on its own HIP stream (and, by default, its own CRE side stream): every
-    result equals the one the model gives alone, bit for bit, while the other model's kernels share the GPU."""
+    result equals the one the model gives alone, bit for bit, while the other model's kernels share the GPU.  With a bf16 and an
+    fp16 model, neither thread's operand type (ops.compute_dtype, per thread) leaks into the other's forward."""
     import threading
     from tests.helpers import SEQ2REG_512, build_model, seq2gene_kw
     from variantformer_amd.utils.synthetic import TISSUES_54, make_batch
     models = [build_model(SEQ2REG_512, seq2gene_kw(layers=6), seed=21 + i).cuda() for i in range(2)]
+    for m, p in zip(models, precisions):
+        m.precision = p
     batches = [make_batch(31 + i, [280 + 40 * i, 64], [120, 30 + 5 * i], [TISSUES_54[:9], TISSUES_54[3:8]], 200) for i in range(2)]
     alone = [m.predict_step(b, 0) for m, b in zip(models, batches)]          # (also the cache-building first forwards)
     alone = [m.predict_step(b, 0) for m, b in zip(models, batches)]

@@ -342,31 +342,38 @@ def test_first_gene_layer_row_map_attention_is_exact(monkeypatch):
         np.testing.assert_array_equal(a["embeddings"][i], c["embeddings"][i])
 
 
-def test_cre_stream_on_a_side_stream_is_bit_identical(monkeypatch):
+def test_cre_stream_on_a_side_stream_is_bit_identical_from_the_first_forward(monkeypatch):
     """runtime.Switches.overlap_cre_stream (the product default): the CRE layers on a side stream beside the gene layers (CRE
     layer i + 1 needs CRE layer i only; gene layer i + 1 needs gene layer i and CRE layer i).  The overlapped path is
-    bit-identical to the single-stream one over repeated calls (the first forward of a configuration runs single-stream by
-    itself: it builds the per-weights caches), a LayerNorm-fold alert raised by a CRE-stream kernel on the side stream still
-    reaches the batch (the model recomputes it), and stale bits on the side stream's flag do not (round-5 advice).  Full
-    depth: test_default_path_is_reproducible_at_full_depth."""
+    bit-identical to the single-stream one from the first forward of a fresh model on (it builds the per-weights caches, on
+    the main stream: weights.build_streams) and over repeated calls that build nothing, a LayerNorm-fold alert raised by a
+    CRE-stream kernel on the side stream still reaches the batch (the model recomputes it), and stale bits on the side
+    stream's flag do not (round-5 advice).  Full depth: test_default_path_is_reproducible_at_full_depth."""
     import variantformer_amd.seq2gene.model_combined_modulator as M
-    from variantformer_amd import ops, runtime
+    from variantformer_amd import ops, runtime, weights
     monkeypatch.delenv("VF_LN_FOLD", raising=False)                    # the alert half needs the fold (default contract)
     monkeypatch.delenv("VF_TRUNK16", raising=False)
     assert runtime.switches().overlap_cre_stream, "the product default runs the CRE layers on the side stream"
+    sides = _count_side_streams(monkeypatch, M)
     model = build_model(SEQ2REG_512, seq2gene_kw(layers=5), seed=3).cuda()
     batch = make_batch(4, [300, 40], [150, 20], [TISSUES_54[:5], [9, 33]], 200)
+    first = model.predict_step(batch, 0)
+    assert len(sides) == 1, "the first forward of a fresh model takes the two-stream path"
+    n = weights.BUILDS
     with runtime.override(overlap_cre_stream=False):
         a = model.predict_step(batch, 0)
-    warm = model.combined_modulator.cre_layers[0].__dict__["_vf_overlap_warm"]
-    assert len(warm) == 1
+    assert len(sides) == 1 and weights.BUILDS == n
+    for i in range(2):
+        np.testing.assert_array_equal(a["pred_gene_exp"][i], first["pred_gene_exp"][i])
+        np.testing.assert_array_equal(a["embeddings"][i], first["embeddings"][i])
     hs = M.heal_state(model)
     for _ in range(3):
         b = model.predict_step(batch, 0)
         for i in range(2):
             np.testing.assert_array_equal(a["pred_gene_exp"][i], b["pred_gene_exp"][i])
             np.testing.assert_array_equal(a["embeddings"][i], b["embeddings"][i])
-    assert hs.batches == 0 and hs.finished == 4
+    assert len(sides) == 4 and weights.BUILDS == n, "a steady two-stream forward built a per-weights cache"
+    assert hs.batches == 0 and hs.finished == 5
     # stale bits on the side stream's flag belong to nobody: the next batch must not be recomputed because of them
     dev = torch.device("cuda", torch.cuda.current_device())
     side = M._side_stream(dev)
@@ -391,6 +398,71 @@ def test_cre_stream_on_a_side_stream_is_bit_identical(monkeypatch):
         np.testing.assert_array_equal(got["pred_gene_exp"][i], want["pred_gene_exp"][i])
 
 
+def _count_side_streams(monkeypatch, M):
+    """Every two-stream forward asks M._side_stream for its side stream once: returns the list of those calls."""
+    calls, real = [], M._side_stream
+    monkeypatch.setattr(M, "_side_stream", lambda *a: calls.append(a) or real(*a))
+    return calls
+
+
+def test_caches_a_two_stream_forward_rebuilds_are_built_on_the_main_stream(monkeypatch):
+    """A per-weights cache that a two-stream forward has to rebuild -- after an in-place weight change (load_state_dict,
+    fine-tuning, bench.py --full's trained_like pass), or after a forward under ln_fold_forced_off() (the LayerNorm-fold
+    recomputation) replaced the folded operands -- is built on the main stream with the two streams joined
+    (weights.build_streams): nothing is built on the side stream, and that forward equals a single-stream forward of the same
+    weights bit for bit."""
+    import variantformer_amd.seq2gene.model_combined_modulator as M
+    from variantformer_amd import runtime, weights
+    from variantformer_amd.seq2gene.modules.layers import ln_fold_forced_off
+    monkeypatch.delenv("VF_LN_FOLD", raising=False)
+    monkeypatch.delenv("VF_TRUNK16", raising=False)
+    sides = _count_side_streams(monkeypatch, M)
+    built_on, real = set(), weights.derived
+
+    def derived(owner, slot, sources, build, *spec):
+        def spy():
+            built_on.add(torch.cuda.current_stream().cuda_stream)
+            return build()
+        return real(owner, slot, sources, spy, *spec)
+    monkeypatch.setattr(weights, "derived", derived)
+    main = torch.cuda.current_stream().cuda_stream
+    model = build_model(SEQ2REG_512, seq2gene_kw(layers=5), seed=4).cuda()
+    batch = make_batch(6, [300, 40], [150, 20], [TISSUES_54[:5], [9, 33]], 200)
+    cm = model.combined_modulator
+    before = model.predict_step(batch, 0)
+    assert len(sides) == 1 and built_on == {main}
+
+    def two_streams_then_one(why):
+        built_on.clear()
+        k, n = len(sides), weights.BUILDS
+        got = model.predict_step(batch, 0)
+        assert len(sides) == k + 1, why + ": the forward must take the two-stream path"
+        assert weights.BUILDS - n >= len(cm.cre_layers), why + ": the CRE-layer caches must have been rebuilt"
+        assert built_on == {main}, why + ": a cache was built off the main stream"
+        n = weights.BUILDS
+        with runtime.override(overlap_cre_stream=False):
+            want = model.predict_step(batch, 0)
+        assert weights.BUILDS == n
+        for i in range(2):
+            np.testing.assert_array_equal(got["pred_gene_exp"][i], want["pred_gene_exp"][i])
+            np.testing.assert_array_equal(got["embeddings"][i], want["embeddings"][i])
+        return got
+    with torch.no_grad():                                            # (a) in place, after warm-up
+        for layer in cm.cre_layers:
+            for p in layer.parameters():
+                if p.dim() == 2:
+                    p.mul_(1.0625)
+        cm.second_level_context_embedding.weight.mul_(0.875)
+    got = two_streams_then_one("after an in-place weight change")
+    assert not np.array_equal(got["embeddings"][0], before["embeddings"][0])
+    built_on.clear()
+    with ln_fold_forced_off():                                       # (b) the unfolded operands replace the folded ones
+        model.predict_step(batch, 0)
+    assert built_on == {main}
+    two_streams_then_one("after a forward with the LayerNorm fold forced off")
+    assert M.heal_state(model).batches == 0
+
+
 def test_default_path_is_reproducible_at_full_depth():
     """The product path at full depth (25 modulator layers, 6 seq2reg layers; CRE layers on the side stream): the same ragged
     batch evaluated three times gives the same bits -- the bits of the single-stream order -- and once more inside a different
@@ -401,7 +473,7 @@ def test_default_path_is_reproducible_at_full_depth():
     assert runtime.switches().overlap_cre_stream
     model, hp, kw = bench.build_model(torch.device("cuda", 0))
     batch = make_batch(77, [700, 90, 311], [150, 20, 64], [TISSUES_54, TISSUES_54[:7], TISSUES_54[:30]], 200)
-    a = model.predict_step(batch, 0)                               # (the first forward builds the caches on one stream)
+    a = model.predict_step(batch, 0)                               # (the first forward also builds the caches)
     for _ in range(3):
         b = model.predict_step(batch, 0)
         for i in range(3):

@@ -5,6 +5,8 @@ hand-written HIP kernel.  All wrappers require CUDA(ROCm) tensors and raise othe
 """
 from __future__ import annotations
 
+import contextlib
+import contextvars
 import math
 
 import torch
@@ -15,30 +17,24 @@ from ._lib import (EPI_BF16, EPI_F32, EPI_GEGLU_BF16, EPI_GELU_BF16, EPI_GELU_F3
 
 # The 16-bit operand type of the GEMM / attention kernels: torch.bfloat16 (the reference's shipped `bf16-mixed`) or
 # torch.float16 (its `16-mixed` / fp16 flash-attn path; BASELINE configs[4]).  fp32 accumulation either way.  The
-# "*_BF16" epilogue names mean "16-bit output in the operand type".
-_CDT = torch.bfloat16
+# "*_BF16" epilogue names mean "16-bit output in the operand type".  Per context, like runtime.Switches (a thread starts with bf16).
+_CDT: contextvars.ContextVar = contextvars.ContextVar("vf_compute_dtype", default=torch.bfloat16)
 
 
-class compute_dtype:
+@contextlib.contextmanager
+def compute_dtype(dtype):
     """with ops.compute_dtype(torch.float16): ...  -- 16-bit tensors created inside (LayerNorm outputs, casts, packed
     weights) use this operand type; kernels themselves follow the dtype of the tensors they are handed."""
-
-    def __init__(self, dtype):
-        assert dtype in (torch.bfloat16, torch.float16), dtype
-        self.dtype = dtype
-
-    def __enter__(self):
-        global _CDT
-        self.prev, _CDT = _CDT, self.dtype
-
-    def __exit__(self, *exc):
-        global _CDT
-        _CDT = self.prev
-        return False
+    assert dtype in (torch.bfloat16, torch.float16), dtype
+    token = _CDT.set(dtype)
+    try:
+        yield
+    finally:
+        _CDT.reset(token)
 
 
 def cdt():
-    return _CDT
+    return _CDT.get()
 
 
 def _is16(dtype) -> bool:
@@ -251,7 +247,7 @@ def ln_fold_abs_limit() -> float:
     """Largest |x| the 16-bit copies of a LayerNorm-folded stream represent: unbounded (0 = no check) when every copy is
     bf16; 60000 / scale for the fp16 copy with the least headroom (fp16 operand copy, fp16 trunk copy)."""
     scales = []
-    if _CDT == torch.float16:
+    if cdt() == torch.float16:
         scales.append(x16_scale_for(torch.float16))
     if runtime.env().trunk16 == "f16":           # VF_TRUNK16, read once per forward (runtime.forward_env)
         scales.append(T16_SCALE)
@@ -283,13 +279,13 @@ def ln_stream(x: torch.Tensor, eps: float = 1e-5, raise_alert: bool = True) -> L
     _dev(x)
     assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
     M, D = x.shape
-    x16 = torch.empty((M, D), dtype=_CDT, device=x.device)
+    x16 = torch.empty((M, D), dtype=cdt(), device=x.device)
     stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
-    scale = x16_scale_for(_CDT)
+    scale = x16_scale_for(x16.dtype)
     alert_ptr = _alert_flag(x.device).data_ptr() if raise_alert else 0
 
     def launch():
-        check(_lib.load().vf_row_stats_cast2(x.data_ptr(), M, D, eps, x16.data_ptr(), _dt(_CDT), scale, LN_FOLD_RATIO_LIMIT,
+        check(_lib.load().vf_row_stats_cast2(x.data_ptr(), M, D, eps, x16.data_ptr(), _dt(x16.dtype), scale, LN_FOLD_RATIO_LIMIT,
                                              ln_fold_abs_limit(), alert_ptr, stats.data_ptr(), _stream()),
               "vf_row_stats_cast")
     if TIMER is not None:
@@ -500,7 +496,7 @@ def softmax_counted(scores: torch.Tensor, log2_count: torch.Tensor, cu_q: torch.
     assert scores.dtype == torch.float32 and scores.stride(1) == 1 and log2_count.dtype == torch.float32 and log2_count.is_contiguous()
     T, n_seq, C = scores.shape[0], cu_q.numel() - 1, log2_count.shape[1]
     assert scores.shape[1] >= n_heads * slots and log2_count.shape[0] == n_seq
-    dt = _CDT if out_dtype is None else out_dtype
+    dt = cdt() if out_dtype is None else out_dtype
     out = torch.empty((T, n_heads * slots), dtype=dt, device=scores.device)
 
     def launch():
@@ -582,7 +578,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtyp
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""
     _dev(x, gamma, beta, out)
-    out_dtype = _CDT if out_dtype is None else out_dtype
+    out_dtype = cdt() if out_dtype is None else out_dtype
     assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
     rows, D = x.shape
     if out is None:
@@ -636,15 +632,15 @@ def embed_stream(ids: torch.Tensor, pad: torch.Tensor, cu: torch.Tensor, table: 
     d = table.shape[1]
     dev = ids.device
     x = torch.empty((n_tokens, d), dtype=torch.float32, device=dev) if need_x else None
-    x16 = torch.empty((n_tokens, d), dtype=_CDT, device=dev)
+    x16 = torch.empty((n_tokens, d), dtype=cdt(), device=dev)
     t16 = torch.empty((n_tokens, d), dtype=torch.float16, device=dev) if need_t16 else None
     stats = torch.empty((n_tokens, 2), dtype=torch.float32, device=dev)
-    scale = x16_scale_for(_CDT)
+    scale = x16_scale_for(x16.dtype)
     alert = _alert_flag(dev)
 
     def launch():
         check(_lib.load().vf_embed_stream(ids.data_ptr(), pad.data_ptr(), cu.data_ptr(), table.data_ptr(), _ptr(pos_table),
-                                          _ptr(x), x16.data_ptr(), _dt(_CDT), scale, _ptr(t16), T16_SCALE, stats.data_ptr(),
+                                          _ptr(x), x16.data_ptr(), _dt(x16.dtype), scale, _ptr(t16), T16_SCALE, stats.data_ptr(),
                                           eps, LN_FOLD_RATIO_LIMIT, ln_fold_abs_limit(), alert.data_ptr(), W, L, d, table.shape[0],
                                           _stream()),
               "vf_embed_stream")
@@ -670,7 +666,7 @@ def token_keys(ids: torch.Tensor, pad: torch.Tensor, cu: torch.Tensor, n_tokens:
 
 def segment_mean(x: torch.Tensor, cu: torch.Tensor, out_dtype=None) -> torch.Tensor:
     _dev(x, cu)
-    out_dtype = _CDT if out_dtype is None else out_dtype
+    out_dtype = cdt() if out_dtype is None else out_dtype
     assert x.dtype == torch.float32 and x.is_contiguous() and cu.dtype == torch.int32
     W = cu.numel() - 1
     out = torch.empty((W, x.shape[1]), dtype=out_dtype, device=x.device)
@@ -708,7 +704,7 @@ def segment_linear(x: torch.Tensor, cu: torch.Tensor, pad: torch.Tensor, lin_w: 
                    out_dtype=None) -> torch.Tensor:
     """seq2reg "linear" pooling: out[w] = sum_p lin_w[p] * x[row(w, p)] over the valid positions p, + lin_b."""
     _dev(x, cu, pad, lin_w, lin_b)
-    out_dtype = _CDT if out_dtype is None else out_dtype
+    out_dtype = cdt() if out_dtype is None else out_dtype
     pad = pad.view(torch.uint8) if pad.dtype == torch.bool else pad
     assert x.dtype == torch.float32 and x.is_contiguous() and cu.dtype == torch.int32 and pad.dtype == torch.uint8
     W, L = pad.shape
@@ -792,7 +788,7 @@ def last_kernel(which: str = "gemm") -> str:
 def cast16(x: torch.Tensor, dtype=None) -> torch.Tensor:
     """fp32 -> 16-bit operand type (default: the current compute dtype), round to nearest even."""
     _dev(x)
-    dtype = _CDT if dtype is None else dtype
+    dtype = cdt() if dtype is None else dtype
     assert x.dtype == torch.float32 and x.is_contiguous() and _is16(dtype)
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
     lib = _lib.load()

@@ -28,11 +28,9 @@ class Switches:
     layer0_qkv_table: bool = True             # seq2reg's first-layer Wqkv by lookup (3.12)
     pool_before_down_projection: bool = True  # seq2reg's mean pool before its last down-projection (3.11)
     overlap_cre_stream: bool = True           # the CRE layers on a side stream beside the gene layers (their small kernels fill the
-                                              # tails of the gene stream's persistent GEMMs: -0.4 ... 0.8 % step time).  Bit-identical
-                                              # to the single-stream order at full depth SINCE the library is built without
-                                              # packed-fp32 instructions (round 6: the run-to-run differences of two streams were a
-                                              # gfx950 hazard of v_pk_*_f32 op_sel forms beside another kernel's MFMAs --
-                                              # csrc/build.py NO_PACKED_FP32, profiles/r06_d_*); False = one stream
+                                              # tails of the gene stream's persistent GEMMs: -0.4 ... 0.8 % step time; weight caches are
+                                              # built on the main stream, weights.py).  Bit-identical to the single-stream order since
+                                              # the library has no packed-fp32 instruction (csrc/build.py); False = one stream
 
 
 _SW: contextvars.ContextVar = contextvars.ContextVar("vf_switches", default=Switches())

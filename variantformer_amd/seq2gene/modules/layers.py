@@ -18,7 +18,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from ... import ops, runtime
+from ... import ops, runtime, weights
 
 
 def get_alibi_slopes(n: int) -> torch.Tensor:
@@ -38,42 +38,36 @@ def get_alibi_slopes(n: int) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------
 # weight packing (fp32 master parameters -> bf16 kernel operands), cached per parameter version
 # ---------------------------------------------------------------------------------------------
-def _row_scale(n_rows: int, scale: float, qrows: int, device):
-    """[n_rows, 1] factor: `scale` for the first `qrows` output rows (all rows when qrows = 0), 1 elsewhere."""
-    v = torch.full((n_rows, 1), float(scale), dtype=torch.float32, device=device)
-    if qrows:
-        v[qrows:] = 1.0
-    return v
+def _pack(lin: nn.Linear, norm, geglu: bool, wscale: float, bscale: float, qrows: int):
+    """The operands of packed_linear (norm None) and packed_linear_ln, from the fp32 masters."""
+    wf = lin.weight.detach().float()
+    def rows(scale):        # [N, 1]: `scale` for the first `qrows` output rows (all rows when qrows = 0), 1 elsewhere
+        v = torch.full((wf.shape[0], 1), float(scale), dtype=torch.float32, device=wf.device)
+        if qrows:
+            v[qrows:] = 1.0
+        return v
+    w = wf if norm is None else wf * norm.weight.detach().float()[None, :]
+    wb = ops.cast16((w if wscale == 1.0 else w * rows(wscale)).contiguous())
+    b = None if norm is None else wf @ norm.bias.detach().float()
+    if lin.bias is not None:
+        b = lin.bias.detach().float() if b is None else b + lin.bias.detach().float()
+    if b is not None:
+        b = (b if bscale == 1.0 else b * rows(bscale)[:, 0]).contiguous()
+    if geglu:
+        wb, b = ops.pack_geglu_rows(wb, b)
+    return (wb, b) if norm is None else (wb, b, wb.float().sum(dim=1).contiguous())
 
 
 def packed_linear(lin: nn.Linear, geglu: bool = False, wscale: float = 1.0, bscale: float = 1.0, qrows: int = 0):
     """(16-bit weight [N,K] in the current compute dtype, fp32 bias [N]) for vf_gemm_*; `geglu` applies the GEGLU row
-    interleave.  Rebuilt whenever the parameter is modified in place (load_state_dict), moved, or the compute dtype
-    changes (one cached copy per module: a model runs in one precision at a time).  `wscale` (a power of two): the
-    16-bit weights are 16bit(W * wscale) -- the operand of a GEMM whose OTHER operand is a stream copy stored scaled by
-    1 / wscale (ops.LnStream.scale, fp16 mode); the product is then the unscaled one, exactly.  `bscale` multiplies the
-    bias (q_prescale passes wscale = bscale = softmax scale * log2 e: the whole projection is scaled).  `qrows` > 0: both
-    scales apply to the first `qrows` output rows only (the Q rows of a packed Wqkv)."""
-    w = lin.weight
-    key = (w.data_ptr(), w._version, str(w.device), geglu, ops.cdt(), float(wscale), float(bscale), int(qrows),
-           None if lin.bias is None else (lin.bias.data_ptr(), lin.bias._version))
-    cache = getattr(lin, "_vf_packed", None)
-    if cache is not None and cache[0] == key:
-        return cache[1], cache[2]
-    with torch.no_grad():
-        wf = w.detach().float()
-        wb = ops.cast16((wf if wscale == 1.0 else wf * _row_scale(wf.shape[0], wscale, qrows, wf.device)).contiguous())
-        b = None
-        if lin.bias is not None:
-            b = lin.bias.detach().float()
-            if bscale != 1.0:
-                b = b * _row_scale(b.shape[0], bscale, qrows, b.device)[:, 0]
-            b = b.contiguous()
-        if geglu:
-            wb, b = ops.pack_geglu_rows(wb, b)
-    lin._vf_packed = (key, wb, b)
-    lin._vf_packed_ln = None          # one operand copy per Linear: a module runs folded or unfolded, not both at once
-    return wb, b
+    interleave.  Cached (weights.derived) in the Linear's one slot, shared with packed_linear_ln: a module runs folded or
+    unfolded, not both at once.  `wscale` (a power of two): the 16-bit weights are 16bit(W * wscale) -- the operand of a
+    GEMM whose OTHER operand is a stream copy stored scaled by 1 / wscale (ops.LnStream.scale, fp16 mode); the product is
+    then the unscaled one, exactly.  `bscale` multiplies the bias (q_prescale passes wscale = bscale = softmax scale *
+    log2 e: the whole projection is scaled).  `qrows` > 0: both scales apply to the first `qrows` output rows only (the Q
+    rows of a packed Wqkv)."""
+    return weights.derived(lin, "_vf_packed", (lin.weight, lin.bias), lambda: _pack(lin, None, geglu, wscale, bscale, qrows),
+                           "plain", geglu, wscale, bscale, qrows)
 
 
 def packed_linear_ln(lin: nn.Linear, norm: nn.LayerNorm, geglu: bool = False, wscale: float = 1.0, qrows: int = 0):
@@ -84,32 +78,10 @@ def packed_linear_ln(lin: nn.Linear, norm: nn.LayerNorm, geglu: bool = False, ws
        so that LN(x) W^T + b = rstd * (x w'^T - mean * colsum) + bias'.  `geglu` applies the GEGLU row interleave to all
        three.  `wscale`: the projection (its first `qrows` output rows; all of them when qrows = 0) multiplied by a constant
        (q_prescale: the softmax scale folded into Wq / the Q rows of Wqkv): w' = 16bit(wscale * gamma (.) W), bias' =
-       wscale * (W . beta + b).  One-time weight
-       preparation (cached per parameter versions), torch elementwise / reduce ops on the fp32 masters; nothing of this
-       runs per batch."""
-    w, g, be = lin.weight, norm.weight, norm.bias
-    key = (w.data_ptr(), w._version, g.data_ptr(), g._version, be.data_ptr(), be._version, str(w.device), geglu, ops.cdt(),
-           float(wscale), int(qrows), None if lin.bias is None else (lin.bias.data_ptr(), lin.bias._version))
-    cache = getattr(lin, "_vf_packed_ln", None)
-    if cache is not None and cache[0] == key:
-        return cache[1], cache[2], cache[3]
-    with torch.no_grad():
-        wf = w.detach().float()
-        wg = wf * g.detach().float()[None, :]
-        rs = None if wscale == 1.0 else _row_scale(wf.shape[0], wscale, qrows, wf.device)   # first `qrows` rows (0: all)
-        wb = ops.cast16((wg if rs is None else wg * rs).contiguous())                # current operand type (bf16 / fp16)
-        b = wf @ be.detach().float()
-        if lin.bias is not None:
-            b = b + lin.bias.detach().float()
-        if rs is not None:
-            b = b * rs[:, 0]
-        b = b.contiguous()
-        if geglu:
-            wb, b = ops.pack_geglu_rows(wb, b)
-        colsum = wb.float().sum(dim=1).contiguous()
-    lin._vf_packed_ln = (key, wb, b, colsum)
-    lin._vf_packed = None             # drop the plain 16-bit copy a previous unfolded / fp16 run may have left
-    return wb, b, colsum
+       wscale * (W . beta + b).  One-time weight preparation (cached in packed_linear's slot), torch elementwise / reduce
+       ops on the fp32 masters; nothing of this runs per batch."""
+    return weights.derived(lin, "_vf_packed", (lin.weight, lin.bias, norm.weight, norm.bias),
+                           lambda: _pack(lin, norm, geglu, wscale, wscale, qrows), "ln", geglu, wscale, qrows)
 
 
 _LN_FOLD_TLS = threading.local()       # .off > 0: this THREAD is inside ln_fold_forced_off() (a recomputation in one thread must
@@ -331,15 +303,9 @@ class MHA(nn.Module):
         Cp = next((c for c in range(C + (C & 1), 17, 2) if (H * c) % 64 == 0), None)
         if Cp is None:
             return None
-        prm = [table, self.Wq.weight, self.Wq.bias, self.Wkv.weight, self.Wkv.bias, self.out_proj.weight, self.out_proj.bias]
-        if norm is not None:
-            prm += [norm.weight, norm.bias]
-        key = (ops.cdt(), norm is not None) + tuple((p.data_ptr(), p._version) for p in prm)
-        slot = "_vf_lowrank_ln" if norm is not None else "_vf_lowrank"
-        c = getattr(self, slot, None)
-        if c is not None and c[0] == key:
-            return c[1]
-        with torch.no_grad():
+        prm = [table, self.Wq.weight, self.Wq.bias, self.Wkv.weight, self.Wkv.bias, self.out_proj.weight, self.out_proj.bias,
+               None if norm is None else norm.weight, None if norm is None else norm.bias]
+        def build():
             kv = table.detach().float() @ self.Wkv.weight.detach().float().t() + self.Wkv.bias.detach().float()     # [C, 2D]
             k, v = kv[:, :D].view(C, H, dh), kv[:, D:].view(C, H, dh)
             wq = self.Wq.weight.detach().float().view(H, dh, D)
@@ -358,9 +324,8 @@ class MHA(nn.Module):
                 cs = wz.float().sum(dim=1).contiguous()
             else:
                 wz, bz, cs = ops.cast16(z.contiguous()), zb.contiguous(), None
-        out = (wz, bz, cs, u16, bo, Cp)
-        setattr(self, slot, (key, out))
-        return out
+            return wz, bz, cs, u16, bo, Cp
+        return weights.derived(self, "_vf_lowrank_ln" if norm is not None else "_vf_lowrank", prm, build)
 
     def cross_lowrank(self, x, norm, table, log2_count, cu_q, max_q, residual, tables=None):
         """out_proj(cross attention of LayerNorm(x) against Wkv(table rows), row c counted 2^log2_count[s, c] times) + residual

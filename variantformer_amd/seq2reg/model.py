@@ -14,7 +14,7 @@ import types
 import torch
 import torch.nn as nn
 
-from .. import ops, runtime
+from .. import ops, runtime, weights
 from .modules import FlashTransformerLayer
 
 
@@ -25,6 +25,7 @@ from .modules import FlashTransformerLayer
 #                                  (Seq2RegPredictor._layer0_qkv_table); off: project every token.
 LAYER0_QKV_TABLE_MAX_BYTES = 1 << 30         # cap on vocab * token_length rows of 3 d 16-bit values, per tokenizer and operand
                                              # type (shipped: 500 x 200 rows x 3 KB = 307 MB); above it every token is projected
+_LAYER0_SLOTS = {torch.bfloat16: "_vf_layer0_qkv_bf16", torch.float16: "_vf_layer0_qkv_fp16"}
 
 
 def positionalencoding1d(d_model: int, length: int) -> torch.Tensor:
@@ -113,28 +114,26 @@ class Seq2RegPredictor(nn.Module):
         pos = self._pos_table(device)
         V = self.token_embedding.weight.shape[0]
         key_L = pos.shape[0] if pos is not None else 1
-        prm = [self.token_embedding.weight, l0.norm1.weight, l0.norm1.bias, l0.MHA.Wqkv.weight, l0.MHA.Wqkv.bias]
-        if pos is not None:
-            prm.append(pos)                                   # the positional table is an input of every row too
-        key = (str(device), key_L) + tuple((p.data_ptr(), p._version) for p in prm)
-        slots = self.__dict__.setdefault("_qkv_tabs", {})    # one slot per operand type (a bf16 <-> fp16 switch rebuilds nothing)
-        hit = slots.get(ops.cdt())
-        if hit is not None and hit[0] == key:
-            return hit[1], key_L
-        for dt in [d for d, v in slots.items() if v[0] != key]:      # tables of previous weights / another device: 307 MB each
-            del slots[dt]                                            # (round-5 advice: they stayed in the other slot forever)
-        ids = torch.arange(V, device=device, dtype=torch.int64).view(V, 1).expand(V, key_L).contiguous()
-        pad = torch.zeros((V, key_L), dtype=torch.uint8, device=device)
-        cu = (torch.arange(V + 1, device=device, dtype=torch.int32) * key_L).contiguous()
-        # rows no token may ever show (unused ids) must not raise the LayerNorm-fold alert: the tokens of a batch raise it
-        # themselves (their own vf_embed_stream pass), and the recomputation does not come through this table
-        alert = ops._alert_flag(device)
-        before = alert.clone()
-        s = ops.embed_stream(ids, pad, cu, self.token_embedding.weight, pos, V * key_L, need_t16=False)
-        alert.copy_(before)
-        w, b, c = l0.MHA.packed_qkv_ln(l0.norm1)
-        slots[ops.cdt()] = (key, ops.gemm_ln_consumer(s, w, b, c, ops.EPI_BF16, family="seq2reg"))
-        return slots[ops.cdt()][1], key_L
+        # (the positional table, when there is one, is an input of every row too)
+        prm = [self.token_embedding.weight, l0.norm1.weight, l0.norm1.bias, l0.MHA.Wqkv.weight, l0.MHA.Wqkv.bias, pos]
+        def build():
+            # one slot per operand type (a bf16 <-> fp16 switch rebuilds nothing); a rebuild first drops every table of previous
+            # weights / another device: 307 MB each (round-5 advice: the other type's stayed there forever)
+            for slot in _LAYER0_SLOTS.values():
+                if not weights.built_from(self, slot, prm, key_L):
+                    self.__dict__.pop(slot, None)
+            ids = torch.arange(V, device=device, dtype=torch.int64).view(V, 1).expand(V, key_L).contiguous()
+            pad = torch.zeros((V, key_L), dtype=torch.uint8, device=device)
+            cu = (torch.arange(V + 1, device=device, dtype=torch.int32) * key_L).contiguous()
+            # rows no token may ever show (unused ids) must not raise the LayerNorm-fold alert: the tokens of a batch raise it
+            # themselves (their own vf_embed_stream pass), and the recomputation does not come through this table
+            alert = ops._alert_flag(device)
+            before = alert.clone()
+            s = ops.embed_stream(ids, pad, cu, self.token_embedding.weight, pos, V * key_L, need_t16=False)
+            alert.copy_(before)
+            w, b, c = l0.MHA.packed_qkv_ln(l0.norm1)
+            return ops.gemm_ln_consumer(s, w, b, c, ops.EPI_BF16, family="seq2reg")
+        return weights.derived(self, _LAYER0_SLOTS[ops.cdt()], prm, build, key_L), key_L
 
     def _layer0_qkv_table_bytes(self) -> int:
         """Size the table of _layer0_qkv_table would have: vocab * key_L rows (key_L = rows of the positional table, NOT the

@@ -4,7 +4,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import ops, weights
 from ..seq2gene.modules.layers import MHA, get_alibi_slopes, packed_linear  # noqa: F401
 
 
@@ -33,14 +33,13 @@ class FlashTransformerLayer(nn.Module):
         never written.  mean(hg) stays fp32-accurate through the 16-bit GEMM as [hi | lo] against [W2 | W2]; the residual
         mean is taken over the very values the token-level epilogue adds: the fp32 rows, or a 16-bit copy times its scale
         (res16: the fp16 trunk copy, or the operand-type copy of the layer input).  -> fp32 [W, d]."""
-        wm = self.linear_geglu_2.weight                  # keyed on the MASTER parameter (as packed_linear is): the packed copy's
-        key = (wm.data_ptr(), wm._version, str(wm.device), ops.cdt())      # address can be reused by its successor
-        if getattr(self, "_w2_split_key", None) != key:
-            self._w2_split, self._w2_split_key = torch.cat([w2, w2], dim=1).contiguous(), key
+        # keyed on the MASTER parameter (as packed_linear is): the packed copy's address can be reused by its successor
+        w2_split = weights.derived(self, "_vf_w2_split", (self.linear_geglu_2.weight,),
+                                   lambda: torch.cat([w2, w2], dim=1).contiguous())
         ph = ops.segment_mean16(hg, cu, split=True)
         pr = ops.segment_mean16(res16, cu, in_scale=res16_scale) if res16 is not None else \
             ops.segment_mean(res_f32, cu, torch.float32)
-        return ops.gemm(ph, self._w2_split, b2, ops.EPI_RES_F32, residual=pr, family="seq2reg")
+        return ops.gemm(ph, w2_split, b2, ops.EPI_RES_F32, residual=pr, family="seq2reg")
 
     def forward_packed(self, src, cu: torch.Tensor, max_seqlen: int, last: bool = False, keep_x: bool = True,
                        pool_mean: bool = False, qkv: tuple | None = None):
