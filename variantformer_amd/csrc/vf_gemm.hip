@@ -162,6 +162,18 @@ __device__ __forceinline__ void ln_emit8(f32x4_t fa, f32x4_t fb, bool valid, uns
     }
 }
 
+// The residual of 4 consecutive columns as fp32, from what was loaded for them: the fp32 values themselves, or
+// (VF_LN_PRODUCER_R16 / _T16) 8 bytes of a 16-bit stream copy, converted (and unscaled) where they are added.
+template <int DT, int LN, class V>
+__device__ __forceinline__ f32x4_t res_value(V v, const LnArgs& ln) {
+    if constexpr (LN == VF_LN_PRODUCER_T16) return cvt4_16<VF_F16>(v) * ln.res16_scale;
+    else if constexpr (ln_res_is_16(LN)) {   // bf16 stream copies are never scaled (checked at launch): no multiply by 1.0 per element
+        if constexpr (DT == VF_F16) return cvt4_16<DT>(v) * ln.res16_scale;
+        else return cvt4_16<DT>(v);
+    }
+    else return v;
+}
+
 // Epilogue of one wave's 128 (m) x 64 (n) accumulator block for the LayerNorm producers whose residual is a 16-bit stream
 // copy (VF_LN_PRODUCER_R16 / _T16), "wide" read-back (round 4): the block is staged as fp32 through `region` in passes of 32
 // rows exactly as before, but a lane reads back EIGHT consecutive columns (two ds_read_b128) of a row instead of four, so the
@@ -204,11 +216,6 @@ __device__ __forceinline__ void producer16_epilogue_wide(f32x4_t (&acc)[4][8], c
             dst[k] = *reinterpret_cast<const u32x4_t*>(rp);
         }
     };
-    auto res_value = [&](u32x2_t v) -> f32x4_t {         // see gemm8_kernel
-        if constexpr (T16) return cvt4_16<VF_F16>(v) * ln.res16_scale;
-        else if constexpr (DT == VF_F16) return cvt4_16<DT>(v) * ln.res16_scale;
-        else return cvt4_16<DT>(v);
-    };
     load_res_pass(0, rbuf[0]);
     f32x4_t bvec[TN];
 #pragma unroll
@@ -235,8 +242,8 @@ __device__ __forceinline__ void producer16_epilogue_wide(f32x4_t (&acc)[4][8], c
         for (int k = 0; k < NI; ++k) {
             const int j = ps * NI + k;                       // row j * RI + ep_row of the wave tile
             const u32x4_t rv = rbuf[ps & 1][k];
-            const f32x4_t fa = __builtin_bit_cast(f32x4_t, da[k]) + res_value((u32x2_t){rv[0], rv[1]});
-            const f32x4_t fb = __builtin_bit_cast(f32x4_t, db[k]) + res_value((u32x2_t){rv[2], rv[3]});
+            const f32x4_t fa = __builtin_bit_cast(f32x4_t, da[k]) + res_value<DT, LN>((u32x2_t){rv[0], rv[1]}, ln);
+            const f32x4_t fb = __builtin_bit_cast(f32x4_t, db[k]) + res_value<DT, LN>((u32x2_t){rv[2], rv[3]}, ln);
             const bool ok = j * RI + ep_row < WT_M && j * RI < rows_left && ep_col < N;
             ln_emit8<DT>(fa, fb, ok, o16_run, part_run, lane, ln.x16_scale, (T16 && ln.t16_out) ? t16_run : nullptr, ln.t16_scale);
             o16_run += o16_step;
@@ -298,6 +305,22 @@ struct Cfg {
     static_assert(STAGES >= 2 && STAGES <= 5 && (STAGES - 2) * LPT <= 48, "vmcnt range");
 };
 
+// Output tile number t of n_tiles -> its origin.  XCD-aware bijective remap: blocks b and b+8 share an XCD (round-robin
+// dispatch), so each XCD gets a contiguous run of tiles; consecutive tiles walk n first and share the A row panel in L2.
+// Grouped order inside the run: GROUP_M m-panels x all n, m fastest, so the ~64 blocks resident on an XCD form a
+// squarish patch (8 A-panels x 8 W-panels) and each staged slice is shared by 8 blocks in that XCD's L2.
+__device__ __forceinline__ void tile_origin(int t, int n_tiles, int tiles_n, int GROUP_M, int BM, int BN, int& m0, int& n0) {
+    const int q8 = n_tiles >> 3, r8 = n_tiles & 7, xcd = t & 7, loc = t >> 3;
+    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    const int tiles_m = n_tiles / tiles_n;
+    const int per_group = GROUP_M * tiles_n;
+    const int grp = wg / per_group, in_grp = wg - grp * per_group;
+    const int first_m = grp * GROUP_M;
+    const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
+    m0 = (first_m + in_grp % gsz) * BM;
+    n0 = (in_grp / gsz) * BN;
+}
+
 template <class C, int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
 __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned short* __restrict__ A, int64_t lda,
                                                               const unsigned short* __restrict__ W,
@@ -310,20 +333,8 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
     constexpr int BM = C::BM, BN = C::BN, TM = C::TM, TN = C::TN, STAGES = C::STAGES, LPT = C::LPT;
     constexpr int BK = C::BK, ROW_BYTES = C::ROW_BYTES, CPR = C::CPR, RPP = C::ROWS_PER_PIECE;
 
-    // XCD-aware bijective remap: blocks b and b+8 share an XCD (round-robin dispatch), so give each
-    // XCD a contiguous run of tiles; consecutive tiles walk n first and share the A row panel in L2.
-    const int bid = blockIdx.x;
-    const int q8 = n_blocks >> 3, r8 = n_blocks & 7, xcd = bid & 7, loc = bid >> 3;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-    // Grouped order inside the run: GROUP_M m-panels x all n, m fastest, so the ~64 blocks resident on an XCD form
-    // a squarish patch (8 A-panels x 8 W-panels) and each staged slice is shared by 8 blocks in that XCD's L2.
-    const int tiles_m = n_blocks / tiles_n;
-    const int per_group = GROUP_M * tiles_n;
-    const int grp = wg / per_group, in_grp = wg - grp * per_group;
-    const int first_m = grp * GROUP_M;
-    const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-    const int tm = first_m + in_grp % gsz, tn = in_grp / gsz;
-    const int m0 = tm * BM, n0 = tn * BN;
+    int m0, n0;
+    tile_origin(blockIdx.x, n_blocks, tiles_n, GROUP_M, BM, BN, m0, n0);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -464,14 +475,6 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
     auto res_load = [&](int64_t m, int col) -> res_t {
         if constexpr (R16) return *reinterpret_cast<const u32x2_t*>(ln.res16 + m * ln.ldr16 + col);
         else return *reinterpret_cast<const f32x4_t*>(res + m * ldr + col);
-    };
-    auto res_value = [&](res_t v) -> f32x4_t {
-        if constexpr (T16) return cvt4_16<VF_F16>(v) * ln.res16_scale;
-        else if constexpr (R16) {        // bf16 stream copies are never scaled (checked at launch): no multiply by 1.0 per element
-            if constexpr (DT == VF_F16) return cvt4_16<DT>(v) * ln.res16_scale;
-            else return cvt4_16<DT>(v);
-        }
-        else return v;
     };
     res_t resv[RES_PRE ? NPASS : 1][RES_PRE ? NI : 1];
     auto prefetch_residual = [&]() {
@@ -652,7 +655,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void gemm_mfma_kernel(const unsigned
                 u32x4_t d = dd[k];
                 if (EPI == VF_EPI_RES_F32) {
                     f32x4_t f = __builtin_bit_cast(f32x4_t, d);
-                    f += res_value(RES_PRE ? resv[RES_PRE ? ps : 0][RES_PRE ? k0 + k : 0] : rbuf[ps & 1][RES_PIPE ? k0 + k : 0]);
+                    f += res_value<DT, LN>(RES_PRE ? resv[RES_PRE ? ps : 0][RES_PRE ? k0 + k : 0] : rbuf[ps & 1][RES_PIPE ? k0 + k : 0], ln);
                     d = __builtin_bit_cast(u32x4_t, f);
                 }
                 const bool ok = ps * RP + row < WT_M && m < M && ep_col < n_out_total;
@@ -707,6 +710,36 @@ struct Cfg8 {
     enum { WL = 0, AL = 1, WH = 2, AH = 3 };
 };
 
+// The phase structure of the two 256 x 256 kernels (used inside them: acc, af, DT are theirs; undefined behind
+// gemm8x_kernel): first barrier of a phase, then the fragment reads must be back, then the MFMA cluster, then the second barrier.
+// sched_barrier(0) keeps hipcc from moving MFMAs or LDS reads across the phase structure; the priority flips keep
+// the cluster together (cdna_hip_programming.md T5).
+#define VF_G8_SYNC_IN()                                          \
+    do {                                                         \
+        asm volatile("" ::: "memory");                           \
+        __builtin_amdgcn_sched_barrier(0);                       \
+        __builtin_amdgcn_s_barrier();                            \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
+        __builtin_amdgcn_sched_barrier(0);                       \
+        __builtin_amdgcn_s_setprio(1);                           \
+    } while (0)
+#define VF_G8_SYNC_OUT()                                         \
+    do {                                                         \
+        __builtin_amdgcn_s_setprio(0);                           \
+        __builtin_amdgcn_sched_barrier(0);                       \
+        __builtin_amdgcn_s_barrier();                            \
+        asm volatile("" ::: "memory");                           \
+        __builtin_amdgcn_sched_barrier(0);                       \
+    } while (0)
+#define VF_G8_MMA(WF, IN0, IM0)                                                                                      \
+    do {                                                                                                             \
+        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                             \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                            \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                        \
+                    acc[IN0 + i][IM0 + j] =                                                                          \
+                        Op16<DT>::mfma(WF[i][ks], af[j][ks], acc[IN0 + i][IM0 + j]); \
+    } while (0)
+
 template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __restrict__ A, int64_t lda,
                                                        const unsigned short* __restrict__ W,
@@ -718,16 +751,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
     using C = Cfg8;
     constexpr int BM = C::BM, BN = C::BN, TM = C::TM, TN = C::TN, BK = C::BK;
 
-    // XCD-aware bijective remap + grouped order (same as gemm_mfma_kernel)
-    const int bid = blockIdx.x;
-    const int q8 = n_blocks >> 3, r8 = n_blocks & 7, xcd = bid & 7, loc = bid >> 3;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-    const int tiles_m = n_blocks / tiles_n;
-    const int per_group = GROUP_M * tiles_n;
-    const int grp = wg / per_group, in_grp = wg - grp * per_group;
-    const int first_m = grp * GROUP_M;
-    const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-    const int m0 = (first_m + in_grp % gsz) * BM, n0 = (in_grp / gsz) * BN;
+    int m0, n0;
+    tile_origin(blockIdx.x, n_blocks, tiles_n, GROUP_M, BM, BN, m0, n0);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -783,35 +808,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
             af[i][1] = *reinterpret_cast<const frag_t*>(b + i * 2048 + ck1);
         }
     };
-    // first barrier of a phase, then the fragment reads must be back, then the MFMA cluster, then the second barrier.
-    // sched_barrier(0) keeps hipcc from moving MFMAs or LDS reads across the phase structure; the priority flips keep
-    // the cluster together (cdna_hip_programming.md T5).
-#define VF_G8_SYNC_IN()                                          \
-    do {                                                         \
-        asm volatile("" ::: "memory");                           \
-        __builtin_amdgcn_sched_barrier(0);                       \
-        __builtin_amdgcn_s_barrier();                            \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
-        __builtin_amdgcn_sched_barrier(0);                       \
-        __builtin_amdgcn_s_setprio(1);                           \
-    } while (0)
-#define VF_G8_SYNC_OUT()                                         \
-    do {                                                         \
-        __builtin_amdgcn_s_setprio(0);                           \
-        __builtin_amdgcn_sched_barrier(0);                       \
-        __builtin_amdgcn_s_barrier();                            \
-        asm volatile("" ::: "memory");                           \
-        __builtin_amdgcn_sched_barrier(0);                       \
-    } while (0)
-#define VF_G8_MMA(WF, IN0, IM0)                                                                                      \
-    do {                                                                                                             \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                             \
-            _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                            \
-                _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                        \
-                    acc[IN0 + i][IM0 + j] =                                                                          \
-                        Op16<DT>::mfma(WF[i][ks], af[j][ks], acc[IN0 + i][IM0 + j]); \
-    } while (0)
-
     // ---- epilogue operands of the tile (bias and, for the LayerNorm consumer, colsum of its 256 columns and (mean,
     // rstd) of its 256 rows) are requested by LDS-DMA BEFORE the first K-tile into a side area behind the ring: they
     // are the oldest entries of every wave's vmcnt queue, so the prologue's wait + barrier publishes them, and the
@@ -884,9 +880,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
     }
     if (wm == 0) __builtin_amdgcn_s_barrier();       // matches group 1's extra barrier: every wave is past its last MFMA
     asm volatile("" ::: "memory");
-#undef VF_G8_SYNC_IN
-#undef VF_G8_SYNC_OUT
-#undef VF_G8_MMA
 
     // ---- epilogue: each wave stages its 128 x 64 block through its own 16 KiB slice of the (now free) ring and
     // writes whole rows, 16 bytes per lane; the fp32 residual rows of pass p+1 are requested while pass p goes through
@@ -950,14 +943,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
                 dst[RES ? k : 0] = *reinterpret_cast<const res_t*>(rp);
             }
         }
-    };
-    auto res_value = [&](res_t v) -> f32x4_t {
-        if constexpr (T16) return cvt4_16<VF_F16>(v) * ln.res16_scale;
-        else if constexpr (R16) {        // bf16 stream copies are never scaled (checked at launch): no multiply by 1.0 per element
-            if constexpr (DT == VF_F16) return cvt4_16<DT>(v) * ln.res16_scale;
-            else return cvt4_16<DT>(v);
-        }
-        else return v;
     };
     load_res_pass(0, rbuf[0]);
     // bias of the wave's columns, from the side area (requested before the first K-tile)
@@ -1052,7 +1037,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(const unsigned short* __r
                 u32x4_t d = dd[k];
                 if (RES) {
                     f32x4_t f = __builtin_bit_cast(f32x4_t, d);
-                    f += res_value(rbuf[ps & 1][RES ? k0 + k : 0]);
+                    f += res_value<DT, LN>(rbuf[ps & 1][RES ? k0 + k : 0], ln);
                     d = __builtin_bit_cast(u32x4_t, f);
                 }
                 const bool ok = j * RI + ep_row < WT_M && j * RI < rows_left && ep_col < n_out_total;
@@ -1093,21 +1078,11 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
     using C = Cfg8;
     constexpr int BM = C::BM, BN = C::BN, TM = C::TM, TN = C::TN, BK = C::BK;
 
-    // XCD-aware bijective remap + grouped order (same as gemm_mfma_kernel)
     const int bid = blockIdx.x;
     const int grid = gridDim.x;
     const int my_tiles = (n_tiles - bid + grid - 1) / grid;          // output tiles bid, bid + grid, ... (>= 1)
-    auto tile_origin = [&](int t, int& m0, int& n0) {                 // XCD-contiguous runs, grouped order (see gemm_mfma_kernel)
-        const int q8 = n_tiles >> 3, r8 = n_tiles & 7, xcd = t & 7, loc = t >> 3;
-        const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-        const int tiles_m = n_tiles / tiles_n;
-        const int per_group = GROUP_M * tiles_n;
-        const int grp = wg / per_group, in_grp = wg - grp * per_group;
-        const int first_m = grp * GROUP_M;
-        const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-        m0 = (first_m + in_grp % gsz) * BM;
-        n0 = (in_grp / gsz) * BN;
-    };
+    // (a lambda and not three direct calls: called directly, hipcc numbers this kernel's registers differently)
+    auto origin = [&](int t, int& m0, int& n0) { tile_origin(t, n_tiles, tiles_n, GROUP_M, BM, BN, m0, n0); };
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1186,39 +1161,10 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
             af[i][1] = *reinterpret_cast<const frag_t*>(b + i * 2048 + ck1);
         }
     };
-    // first barrier of a phase, then the fragment reads must be back, then the MFMA cluster, then the second barrier.
-    // sched_barrier(0) keeps hipcc from moving MFMAs or LDS reads across the phase structure; the priority flips keep
-    // the cluster together (cdna_hip_programming.md T5).
-#define VF_G8_SYNC_IN()                                          \
-    do {                                                         \
-        asm volatile("" ::: "memory");                           \
-        __builtin_amdgcn_sched_barrier(0);                       \
-        __builtin_amdgcn_s_barrier();                            \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
-        __builtin_amdgcn_sched_barrier(0);                       \
-        __builtin_amdgcn_s_setprio(1);                           \
-    } while (0)
-#define VF_G8_SYNC_OUT()                                         \
-    do {                                                         \
-        __builtin_amdgcn_s_setprio(0);                           \
-        __builtin_amdgcn_sched_barrier(0);                       \
-        __builtin_amdgcn_s_barrier();                            \
-        asm volatile("" ::: "memory");                           \
-        __builtin_amdgcn_sched_barrier(0);                       \
-    } while (0)
-#define VF_G8_MMA(WF, IN0, IM0)                                                                                      \
-    do {                                                                                                             \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                             \
-            _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                            \
-                _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                        \
-                    acc[IN0 + i][IM0 + j] =                                                                          \
-                        Op16<DT>::mfma(WF[i][ks], af[j][ks], acc[IN0 + i][IM0 + j]); \
-    } while (0)
-
     // ---- first tile: its epilogue operands and K-tile 0
     const int nkt = K / BK;                                  // >= 2 (launcher)
     int m0, n0;
-    tile_origin(bid, m0, n0);
+    origin(bid, m0, n0);
     set_src(m0, n0);
     issue_side(m0, n0, 0);
     issue(0, 0, C::WL); issue(0, 0, C::AL); issue(0, 0, C::WH); issue(0, 0, C::AH);
@@ -1226,7 +1172,7 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
     int g0 = 0;                                              // stream index of the current tile's K-tile 0
     for (int ti = 0; ti < my_tiles; ++ti) {
         const bool has_next = ti + 1 < my_tiles;             // block-uniform
-        tile_origin(bid + ti * grid, m0, n0);
+        origin(bid + ti * grid, m0, n0);
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
@@ -1257,7 +1203,7 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
             VF_G8_SYNC_OUT();
             if (t + 2 == nkt && has_next) {                          // the stream crosses into the next output tile
                 int m1, n1;
-                tile_origin(bid + (ti + 1) * grid, m1, n1);
+                origin(bid + (ti + 1) * grid, m1, n1);
                 set_src(m1, n1);
                 issue_side(m1, n1, ti + 1);
             }
@@ -1369,14 +1315,6 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
                 }
             }
         };
-        auto res_value = [&](res_t v) -> f32x4_t {      // see gemm8_kernel
-            if constexpr (T16) return cvt4_16<VF_F16>(v) * ln.res16_scale;
-            else if constexpr (R16) {
-                if constexpr (DT == VF_F16) return cvt4_16<DT>(v) * ln.res16_scale;
-                else return cvt4_16<DT>(v);
-            }
-            else return v;
-        };
         load_res_pass(0, rbuf[0]);
         // bias of the wave's columns, from the side area (requested before the first K-tile)
         f32x4_t bvec[TN];
@@ -1465,7 +1403,7 @@ __global__ __launch_bounds__(512, 2) void gemm8x_kernel(const unsigned short* __
                     u32x4_t d = dd[k];
                     if (RES) {
                         f32x4_t f = __builtin_bit_cast(f32x4_t, d);
-                        f += res_value(rbuf[ps & 1][RES ? k0 + k : 0]);
+                        f += res_value<DT, LN>(rbuf[ps & 1][RES ? k0 + k : 0], ln);
                         d = __builtin_bit_cast(u32x4_t, f);
                     }
                     const bool ok = j * RI + ep_row < WT_M && j * RI < rows_left && ep_col < n_out_total;
@@ -1556,73 +1494,54 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(const unsigned short*
 using CfgA = Cfg<128, 128, 2, 2, 2>;       // 64 KiB, 4 waves, 2 blocks/CU
 using CfgE = Cfg<64, 64, 2, 2, 4>;         // 64 KiB, small-M shapes, 2 blocks/CU
 
-template <class C, int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
-int launch_cfg(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
-               int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
-    static bool attr_set[VF_MAX_DEVICES] = {};    // per (config, epilogue) instantiation AND per device
-    auto kern = gemm_mfma_kernel<C, EPI, DT, LN>;
-    const int dev = vf_current_device();
-    if (dev < 0 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                C::LDS_BYTES) != hipSuccess) {
-            (void)hipGetLastError();
-            vf_set_error("vf_gemm_bf16: cannot reserve %d bytes of LDS", C::LDS_BYTES);
-            return VF_ERR_LAUNCH;
-        }
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    const int tiles_m = (M + C::BM - 1) / C::BM, tiles_n = (N + C::BN - 1) / C::BN;
-    const int n_blocks = tiles_m * tiles_n;
-    const int group_m = 8;      // m-panels per L2 group; 2 / 4 / 16 measured equal or slower for both tile sizes
-    vf_note_kernel(0, C::BM == 128 ? "gemm_mfma_kernel<128x128>" : C::BM == 64 ? "gemm_mfma_kernel<64x64>" : "gemm_mfma_kernel<other>");
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(C::THREADS), C::LDS_BYTES, st, (const unsigned short*)A, lda,
-                       (const unsigned short*)W, bias, res, ldr, out, ldo, M, N, K, tiles_n, n_blocks, group_m, ln);
-    VF_CHECK_LAUNCH("vf_gemm_bf16");
-    return VF_OK;
-}
-
-template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
-int launch_gemm8(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
-                 int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
+// Launch KERN with LDS bytes of dynamic LDS: reserve them once per kernel instantiation AND per device (dev = the current
+// device, -1 = unknown: redo the idempotent reservation), note the kernel's name for the profile tables, launch, check.
+template <auto KERN, int LDS, class... Args>
+int launch_with_lds(int dev, const char* name, int grid, int threads, hipStream_t st, Args... args) {
     static bool attr_set[VF_MAX_DEVICES] = {};
-    auto kern = gemm8_kernel<EPI, DT, LN>;
-    const int dev = vf_current_device();
     if (dev < 0 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                Cfg8::LDS_BYTES + Cfg8::SIDE_BYTES) != hipSuccess) {
-            (void)hipGetLastError();
-            vf_set_error("vf_gemm_bf16: cannot reserve %d bytes of LDS", Cfg8::LDS_BYTES + Cfg8::SIDE_BYTES);
-            return VF_ERR_LAUNCH;
-        }
-        if (dev >= 0) attr_set[dev] = true;
-    }
-    const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
-    const int n_blocks = tiles_m * tiles_n;
-    const int group_m = 8;
-    vf_note_kernel(0, "gemm8_kernel");
-    hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(512), Cfg8::LDS_BYTES + Cfg8::SIDE_BYTES, st, (const unsigned short*)A, lda,
-                       (const unsigned short*)W, bias, res, ldr, out, ldo, M, N, K, tiles_n, n_blocks, group_m, ln);
-    VF_CHECK_LAUNCH("vf_gemm_bf16");
-    return VF_OK;
-}
-
-template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
-int launch_gemm8x(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
-                  int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
-    constexpr int LDS = Cfg8::LDS_BYTES + Cfg8::SPARE_BYTES + 2 * Cfg8::SIDE_BYTES;      // 160 KiB: all of a CU's LDS
-    static bool attr_set[VF_MAX_DEVICES] = {};
-    static int n_cu[VF_MAX_DEVICES] = {};
-    auto kern = gemm8x_kernel<EPI, DT, LN>;
-    const int dev = vf_current_device();
-    if (dev < 0 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) !=
-            hipSuccess) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
             (void)hipGetLastError();
             vf_set_error("vf_gemm_bf16: cannot reserve %d bytes of LDS", LDS);
             return VF_ERR_LAUNCH;
         }
         if (dev >= 0) attr_set[dev] = true;
     }
+    vf_note_kernel(0, name);
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(threads), LDS, st, args...);
+    VF_CHECK_LAUNCH("vf_gemm_bf16");
+    return VF_OK;
+}
+
+template <class C, int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
+int launch_cfg(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
+               int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
+    const int tiles_m = (M + C::BM - 1) / C::BM, tiles_n = (N + C::BN - 1) / C::BN;
+    const int n_blocks = tiles_m * tiles_n;
+    const int group_m = 8;      // m-panels per L2 group; 2 / 4 / 16 measured equal or slower for both tile sizes
+    return launch_with_lds<gemm_mfma_kernel<C, EPI, DT, LN>, C::LDS_BYTES>(
+        vf_current_device(), C::BM == 128 ? "gemm_mfma_kernel<128x128>" : C::BM == 64 ? "gemm_mfma_kernel<64x64>" : "gemm_mfma_kernel<other>",
+        n_blocks, C::THREADS, st, (const unsigned short*)A, lda, (const unsigned short*)W, bias, res, ldr, out, ldo, M, N, K,
+        tiles_n, n_blocks, group_m, ln);
+}
+
+template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
+int launch_gemm8(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
+                 int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
+    const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
+    const int n_blocks = tiles_m * tiles_n;
+    const int group_m = 8;
+    return launch_with_lds<gemm8_kernel<EPI, DT, LN>, Cfg8::LDS_BYTES + Cfg8::SIDE_BYTES>(
+        vf_current_device(), "gemm8_kernel", n_blocks, 512, st, (const unsigned short*)A, lda, (const unsigned short*)W, bias, res,
+        ldr, out, ldo, M, N, K, tiles_n, n_blocks, group_m, ln);
+}
+
+template <int EPI, int DT = VF_BF16, int LN = VF_LN_NONE>
+int launch_gemm8x(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
+                  int64_t ldo, int M, int N, int K, hipStream_t st, LnArgs ln = LnArgs{}) {
+    constexpr int LDS = Cfg8::LDS_BYTES + Cfg8::SPARE_BYTES + 2 * Cfg8::SIDE_BYTES;      // 160 KiB: all of a CU's LDS
+    static int n_cu[VF_MAX_DEVICES] = {};
+    const int dev = vf_current_device();
     int cus = 256;
     if (dev >= 0) {
         if (n_cu[dev] == 0) {
@@ -1636,11 +1555,9 @@ int launch_gemm8x(const void* A, int64_t lda, const void* W, const float* bias, 
     const int n_tiles = tiles_m * tiles_n;
     const int grid = n_tiles < cus ? n_tiles : cus;              // one resident block per CU
     const int group_m = 8;
-    vf_note_kernel(0, "gemm8x_kernel");
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS, st, (const unsigned short*)A, lda, (const unsigned short*)W, bias,
-                       res, ldr, out, ldo, M, N, K, tiles_n, n_tiles, group_m, ln);
-    VF_CHECK_LAUNCH("vf_gemm_bf16");
-    return VF_OK;
+    return launch_with_lds<gemm8x_kernel<EPI, DT, LN>, LDS>(dev, "gemm8x_kernel", grid, 512, st, (const unsigned short*)A, lda,
+                                                            (const unsigned short*)W, bias, res, ldr, out, ldo, M, N, K, tiles_n,
+                                                            n_tiles, group_m, ln);
 }
 
 // Tile choice (measured on MI355X, scripts/gemm_bench.py, random data; the cost model inside reproduces every measured
