@@ -47,7 +47,7 @@ with torch.no_grad():
     qkv_h = ops.gemm(h_h, w, b, ops.EPI_BF16)
     qkv_o = rnd.r(O.linear(h_o, sd[pfx+"MHA.Wqkv.weight"], sd[pfx+"MHA.Wqkv.bias"], rnd))
     print(" qkv", rel(qkv_h.float().cpu(), qkv_o), "mismatch frac", float((qkv_h.float().cpu()!=qkv_o).float().mean()))
-    a_h = lay.MHA.attend(h_h, None, cu, 200, None, None)
+    a_h = lay.MHA.attend(h_h, None, None, cu, 200)
     D = hp.embedding_dim; H = hp.num_heads
     a_o = torch.zeros_like(qkv_o[:, :D])
     q3 = qkv_o.view(-1, 3, H, D//H)

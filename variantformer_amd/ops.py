@@ -105,6 +105,16 @@ class scope:
         return False
 
 
+def _run(launch, record) -> None:
+    """launch(), bracketed by the installed KernelTimer if there is one (ops.TIMER).  record() -> (name, flops, bytes,
+    geometry, family) as KernelTimer.time takes them; evaluated only when a timer is installed."""
+    if TIMER is not None:
+        name, flops, nbytes, geometry, family = record()
+        TIMER.time(name, flops, nbytes, launch, geometry, family)
+    else:
+        launch()
+
+
 def _dev(*ts):
     """Every tensor must live on the CURRENT device: the C ABI launches on torch's current stream and never switches
     devices (one process per GPU; use torch.cuda.set_device / torch.cuda.device(...) around calls otherwise)."""
@@ -170,11 +180,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, epilogue: 
             fn = lib.vf_gemm_f16 if f16 else lib.vf_gemm_bf16
             check(fn(a.data_ptr(), lda, w.data_ptr(), _ptr(bias), _ptr(residual), ldr, out.data_ptr(),
                      ldo, M, N, K, epilogue, _stream()), "vf_gemm")
-    if TIMER is not None:
-        nbytes = 2.0 * (M * K + N * K) + out.numel() * out.element_size() + (0 if residual is None else 4.0 * M * N)
-        TIMER.time("gemm", 2.0 * M * N * K, nbytes, launch, f"M={M} N={N} K={K} epi={epilogue}", family or _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("gemm", 2.0 * M * N * K,
+                          2.0 * (M * K + N * K) + out.numel() * out.element_size() + (0 if residual is None else 4.0 * M * N),
+                          f"M={M} N={N} K={K} epi={epilogue}", family or _SCOPE))
     return out
 
 
@@ -288,10 +296,7 @@ def ln_stream(x: torch.Tensor, eps: float = 1e-5, raise_alert: bool = True) -> L
         check(_lib.load().vf_row_stats_cast2(x.data_ptr(), M, D, eps, x16.data_ptr(), _dt(x16.dtype), scale, LN_FOLD_RATIO_LIMIT,
                                              ln_fold_abs_limit(), alert_ptr, stats.data_ptr(), _stream()),
               "vf_row_stats_cast")
-    if TIMER is not None:
-        TIMER.time("layernorm", 0.0, float(M) * D * 6, launch, f"stats_cast D={D}", _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("layernorm", 0.0, float(M) * D * 6, f"stats_cast D={D}", _SCOPE))
     return LnStream(x, x16, stats, scale)
 
 
@@ -321,10 +326,7 @@ def trunk16_of(x: torch.Tensor, raise_alert: bool = True) -> torch.Tensor:
         check(_lib.load().vf_row_stats_cast2(x.data_ptr(), M, D, 1e-5, t16.data_ptr(), VF_F16, T16_SCALE, 1e30,
                                              60000.0 / T16_SCALE, alert_ptr, stats.data_ptr(), _stream()),
               "vf_row_stats_cast")
-    if TIMER is not None:
-        TIMER.time("layernorm", 0.0, float(M) * D * 6, launch, f"trunk16_of D={D}", _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("layernorm", 0.0, float(M) * D * 6, f"trunk16_of D={D}", _SCOPE))
     return t16
 
 
@@ -347,11 +349,8 @@ def gemm_ln_consumer(s: LnStream, w: torch.Tensor, bias: torch.Tensor, colsum: t
         check(lib.vf_gemm_ln(a.data_ptr(), a.stride(0) if M > 1 else max(a.stride(0), K), w.data_ptr(), bias.data_ptr(),
                              0, 0, VF_F32, out.data_ptr(), n_out, M, N, K, epilogue, _dt(a.dtype), s.stats.data_ptr(),
                              colsum.data_ptr(), 0, 0, 0, 1.0, 1.0, _stream()), "vf_gemm_ln")
-    if TIMER is not None:
-        nbytes = 2.0 * (M * K + N * K) + out.numel() * out.element_size() + 8.0 * M
-        TIMER.time("gemm", 2.0 * M * N * K, nbytes, launch, f"M={M} N={N} K={K} epi={epilogue} ln=consumer", family or _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("gemm", 2.0 * M * N * K, 2.0 * (M * K + N * K) + out.numel() * out.element_size() + 8.0 * M,
+                          f"M={M} N={N} K={K} epi={epilogue} ln=consumer", family or _SCOPE))
     return out
 
 
@@ -364,61 +363,13 @@ def gemm_ln_producer(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None
     layer's intermediate stream feeds only the next LayerNorm -> Linear pair) and is not stored; .x is None.
     `trunk16` (instead of `residual`): the residual as the fp16 trunk copy fp16(r * T16_SCALE) of the layer input
     (vf_gemm_ln_t16); need_t16: also write that copy of the result (.t16) for the next layer."""
-    if trunk16 is not None:
-        assert residual is None
-        return _gemm_ln_producer_t16(a, w, bias, trunk16, eps, family, need_x, need_t16)
-    assert not need_t16
+    assert residual is None if trunk16 is not None else not need_t16
     res16 = residual if isinstance(residual, LnStream) else None
     res32 = None if res16 is not None else residual
-    _dev(a, w, bias, res32, None if res16 is None else res16.x16)
+    _dev(a, w, bias, res32, None if res16 is None else res16.x16, trunk16)
     assert _is16(a.dtype) and w.dtype == a.dtype and a.shape[1] == w.shape[1] and a.stride(1) == 1
     M, K = a.shape
     N = w.shape[0]
-    out = torch.empty((M, N), dtype=torch.float32, device=a.device) if need_x else None
-    x16 = torch.empty((M, N), dtype=a.dtype, device=a.device)
-    n_parts = (N + 31) // 32
-    part = torch.empty((n_parts, M, 2), dtype=torch.float32, device=a.device)
-    stats = torch.empty((M, 2), dtype=torch.float32, device=a.device)
-    epi = EPI_F32 if residual is None else EPI_RES_F32
-    if res32 is not None:
-        assert res32.dtype == torch.float32 and res32.shape == (M, N) and res32.stride(1) == 1
-        r_ptr, r_ld, r_dt, r_scale = res32.data_ptr(), res32.stride(0), VF_F32, 1.0
-    elif res16 is not None:
-        r = res16.x16
-        assert r.dtype == a.dtype and r.shape == (M, N) and r.stride(1) == 1
-        r_ptr, r_ld, r_dt, r_scale = r.data_ptr(), r.stride(0), _dt(r.dtype), 1.0 / res16.scale
-    else:
-        r_ptr, r_ld, r_dt, r_scale = 0, 0, VF_F32, 1.0
-    scale = x16_scale_for(a.dtype)
-    alert = _alert_flag(a.device)
-    lib = _lib.load()
-
-    def launch():
-        check(lib.vf_gemm_ln(a.data_ptr(), a.stride(0) if M > 1 else max(a.stride(0), K), w.data_ptr(), _ptr(bias),
-                             r_ptr, r_ld, r_dt, _ptr(out), N, M, N, K, epi, _dt(a.dtype), 0, 0, x16.data_ptr(), N,
-                             part.data_ptr(), scale, r_scale, _stream()), "vf_gemm_ln")
-
-    def finalize():
-        check(lib.vf_ln_finalize2(part.data_ptr(), M, n_parts, N, eps, scale, LN_FOLD_RATIO_LIMIT, ln_fold_abs_limit(),
-                                  alert.data_ptr(), stats.data_ptr(), _stream()), "vf_ln_finalize")
-    if TIMER is not None:
-        res_bytes = 0.0 if residual is None else (4.0 if res32 is not None else 2.0) * M * N
-        nbytes = 2.0 * (M * K + N * K) + M * N * ((4.0 if need_x else 0.0) + 2.0) + res_bytes + 8.0 * M * n_parts
-        tag = "producer" + ("" if need_x else "-nox") + ("-r16" if res16 is not None else "")
-        TIMER.time("gemm", 2.0 * M * N * K, nbytes, launch, f"M={M} N={N} K={K} epi={epi} ln={tag}", family or _SCOPE)
-        TIMER.time("layernorm", 0.0, 8.0 * M * (n_parts + 1), finalize, f"finalize D={N}", _SCOPE)
-    else:
-        launch()
-        finalize()
-    return LnStream(out, x16, stats, scale)
-
-
-def _gemm_ln_producer_t16(a, w, bias, t_in, eps, family, need_x, need_t16) -> LnStream:
-    _dev(a, w, bias, t_in)
-    assert _is16(a.dtype) and w.dtype == a.dtype and a.shape[1] == w.shape[1] and a.stride(1) == 1
-    M, K = a.shape
-    N = w.shape[0]
-    assert t_in.dtype == torch.float16 and t_in.shape == (M, N) and t_in.stride(1) == 1
     out = torch.empty((M, N), dtype=torch.float32, device=a.device) if need_x else None
     t_out = torch.empty((M, N), dtype=torch.float16, device=a.device) if need_t16 else None
     x16 = torch.empty((M, N), dtype=a.dtype, device=a.device)
@@ -428,24 +379,39 @@ def _gemm_ln_producer_t16(a, w, bias, t_in, eps, family, need_x, need_t16) -> Ln
     scale = x16_scale_for(a.dtype)
     alert = _alert_flag(a.device)
     lib = _lib.load()
+    lda = a.stride(0) if M > 1 else max(a.stride(0), K)
+    if trunk16 is not None:
+        assert trunk16.dtype == torch.float16 and trunk16.shape == (M, N) and trunk16.stride(1) == 1
+        epi, res_bytes = EPI_RES_F32, (2.0 + (2.0 if need_t16 else 0.0)) * M * N
+        tag = "-t16" + ("" if need_t16 else "-in")
 
-    def launch():
-        check(lib.vf_gemm_ln_t16(a.data_ptr(), a.stride(0) if M > 1 else max(a.stride(0), K), w.data_ptr(), _ptr(bias),
-                                 t_in.data_ptr(), t_in.stride(0), 1.0 / T16_SCALE, _ptr(out), N, M, N, K, _dt(a.dtype),
-                                 x16.data_ptr(), N, part.data_ptr(), scale, _ptr(t_out), N, T16_SCALE, _stream()),
-              "vf_gemm_ln_t16")
+        def launch():
+            check(lib.vf_gemm_ln_t16(a.data_ptr(), lda, w.data_ptr(), _ptr(bias), trunk16.data_ptr(), trunk16.stride(0),
+                                     1.0 / T16_SCALE, _ptr(out), N, M, N, K, _dt(a.dtype), x16.data_ptr(), N, part.data_ptr(),
+                                     scale, _ptr(t_out), N, T16_SCALE, _stream()), "vf_gemm_ln_t16")
+    else:
+        epi = EPI_F32 if residual is None else EPI_RES_F32
+        if res32 is not None:
+            assert res32.dtype == torch.float32 and res32.shape == (M, N) and res32.stride(1) == 1
+            r_ptr, r_ld, r_dt, r_scale, res_bytes, tag = res32.data_ptr(), res32.stride(0), VF_F32, 1.0, 4.0 * M * N, ""
+        elif res16 is not None:
+            r = res16.x16
+            assert r.dtype == a.dtype and r.shape == (M, N) and r.stride(1) == 1
+            r_ptr, r_ld, r_dt, r_scale, res_bytes, tag = r.data_ptr(), r.stride(0), _dt(r.dtype), 1.0 / res16.scale, 2.0 * M * N, "-r16"
+        else:
+            r_ptr, r_ld, r_dt, r_scale, res_bytes, tag = 0, 0, VF_F32, 1.0, 0.0, ""
+
+        def launch():
+            check(lib.vf_gemm_ln(a.data_ptr(), lda, w.data_ptr(), _ptr(bias), r_ptr, r_ld, r_dt, _ptr(out), N, M, N, K, epi,
+                                 _dt(a.dtype), 0, 0, x16.data_ptr(), N, part.data_ptr(), scale, r_scale, _stream()), "vf_gemm_ln")
 
     def finalize():
         check(lib.vf_ln_finalize2(part.data_ptr(), M, n_parts, N, eps, scale, LN_FOLD_RATIO_LIMIT, ln_fold_abs_limit(),
                                   alert.data_ptr(), stats.data_ptr(), _stream()), "vf_ln_finalize")
-    if TIMER is not None:
-        nbytes = 2.0 * (M * K + N * K) + M * N * ((4.0 if need_x else 0.0) + (2.0 if need_t16 else 0.0) + 2.0 + 2.0) + 8.0 * M * n_parts
-        tag = "producer" + ("" if need_x else "-nox") + "-t16" + ("" if need_t16 else "-in")
-        TIMER.time("gemm", 2.0 * M * N * K, nbytes, launch, f"M={M} N={N} K={K} epi={EPI_RES_F32} ln={tag}", family or _SCOPE)
-        TIMER.time("layernorm", 0.0, 8.0 * M * (n_parts + 1), finalize, f"finalize D={N}", _SCOPE)
-    else:
-        launch()
-        finalize()
+    _run(launch, lambda: ("gemm", 2.0 * M * N * K,
+                          2.0 * (M * K + N * K) + M * N * ((4.0 if need_x else 0.0) + 2.0) + res_bytes + 8.0 * M * n_parts,
+                          f"M={M} N={N} K={K} epi={epi} ln=producer{'' if need_x else '-nox'}{tag}", family or _SCOPE))
+    _run(finalize, lambda: ("layernorm", 0.0, 8.0 * M * (n_parts + 1), f"finalize D={N}", _SCOPE))
     return LnStream(out, x16, stats, scale, t_out)
 
 
@@ -480,11 +446,8 @@ def attn_counted_keys(q: torch.Tensor, kv_table: torch.Tensor, log2_count: torch
         check(_lib.load().vf_attn_counted_keys(q.data_ptr(), q.stride(0), kv_table.data_ptr(), kv_table.stride(0),
                                                log2_count.data_ptr(), cu_q.data_ptr(), n_seq, int(max_q), C, n_heads, head_dim,
                                                out.data_ptr(), out.stride(0), _dt(q.dtype), _stream()), "vf_attn_counted_keys")
-    if TIMER is not None:       # executed work: 4 * tokens * C * width
-        TIMER.time("attn", 4.0 * q.shape[0] * C * D, 2.0 * D * 2 * q.shape[0], launch,
-                   f"H={n_heads} dh={head_dim} max_q={int(max_q)} counted_keys={C}", family or _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("attn", 4.0 * q.shape[0] * C * D, 2.0 * D * 2 * q.shape[0],       # executed work: 4 * tokens * C * width
+                          f"H={n_heads} dh={head_dim} max_q={int(max_q)} counted_keys={C}", family or _SCOPE))
     return out
 
 
@@ -503,10 +466,7 @@ def softmax_counted(scores: torch.Tensor, log2_count: torch.Tensor, cu_q: torch.
         check(_lib.load().vf_softmax_counted(scores.data_ptr(), scores.stride(0), log2_count.data_ptr(), cu_q.data_ptr(), n_seq,
                                              int(max_q), n_heads, slots, C, out.data_ptr(), out.stride(0), _dt(dt), _stream()),
               "vf_softmax_counted")
-    if TIMER is not None:
-        TIMER.time("attn", 0.0, float(T) * n_heads * slots * 6, launch, f"softmax_counted H={n_heads} C={C}", family or _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("attn", 0.0, float(T) * n_heads * slots * 6, f"softmax_counted H={n_heads} C={C}", family or _SCOPE))
     return out
 
 
@@ -561,16 +521,14 @@ def attn_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_q: torch.T
                   v.stride(0), out.stride(0), cu_q.data_ptr(), _ptr(cu_k), cu_q.numel() - 1, int(max_q),
                   int(max_k), n_heads, head_dim, _ptr(slopes), float(scale), _dt(q.dtype), flags,
                   _stream()), "vf_attn_varlen_fwd")
-    if TIMER is not None:
-        def flops():       # 4 * sum_seq(len_q * len_k) * H * dh (QK^T and PV), evaluated after the timed replay
-            lq = (cu_q[1:] - cu_q[:-1]).double()
-            lk = lq if cu_k is None else (cu_k[1:] - cu_k[:-1]).double()
-            return 4.0 * float((lq * lk).sum().item()) * D
-        TIMER.time("attn", flops, 2.0 * D * (2 * tq + 2 * tk), launch,
-                   f"H={n_heads} dh={head_dim} max_q={int(max_q)} max_k={int(max_k)}" + (" rows" if rows is not None else ""),
-                   family or _SCOPE)
-    else:
-        launch()
+
+    def flops():       # 4 * sum_seq(len_q * len_k) * H * dh (QK^T and PV), evaluated after the timed replay
+        lq = (cu_q[1:] - cu_q[:-1]).double()
+        lk = lq if cu_k is None else (cu_k[1:] - cu_k[:-1]).double()
+        return 4.0 * float((lq * lk).sum().item()) * D
+    _run(launch, lambda: ("attn", flops, 2.0 * D * (2 * tq + 2 * tk),
+                          f"H={n_heads} dh={head_dim} max_q={int(max_q)} max_k={int(max_k)}" + (" rows" if rows is not None else ""),
+                          family or _SCOPE))
     return out
 
 
@@ -587,10 +545,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtyp
     def launch():
         check(_lib.load().vf_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), rows, D, eps,
                                        _dt(out.dtype), int(gelu), _stream()), "vf_layernorm")
-    if TIMER is not None:
-        TIMER.time("layernorm", 0.0, float(rows) * D * (4 + out.element_size()), launch, f"D={D}", _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("layernorm", 0.0, float(rows) * D * (4 + out.element_size()), f"D={D}", _SCOPE))
     return out
 
 
@@ -644,11 +599,8 @@ def embed_stream(ids: torch.Tensor, pad: torch.Tensor, cu: torch.Tensor, table: 
                                           eps, LN_FOLD_RATIO_LIMIT, ln_fold_abs_limit(), alert.data_ptr(), W, L, d, table.shape[0],
                                           _stream()),
               "vf_embed_stream")
-    if TIMER is not None:
-        TIMER.time("layernorm", 0.0, float(n_tokens) * d * (2 + (2 if need_t16 else 0) + (4 if need_x else 0)), launch,
-                   f"embed_stream D={d}", _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("layernorm", 0.0, float(n_tokens) * d * (2 + (2 if need_t16 else 0) + (4 if need_x else 0)),
+                          f"embed_stream D={d}", _SCOPE))
     return LnStream(x, x16, stats, scale, t16)
 
 
@@ -762,10 +714,7 @@ def gather_rows_bf16(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     def launch():
         check(_lib.load().vf_gather_rows_bf16(src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), out.stride(0),
                                               idx.numel(), src.shape[1], _stream()), "vf_gather_rows_bf16")
-    if TIMER is not None:
-        TIMER.time("layernorm", 0.0, float(idx.numel()) * (src.shape[1] * 4 + 8), launch, f"gather_rows16 D={src.shape[1]}", _SCOPE)
-    else:
-        launch()
+    _run(launch, lambda: ("layernorm", 0.0, float(idx.numel()) * (src.shape[1] * 4 + 8), f"gather_rows16 D={src.shape[1]}", _SCOPE))
     return out
 
 

@@ -31,8 +31,8 @@ from .. import _lib, ops, runtime, weights
 from ..utils.constants import REF_CREs
 from ..utils.functions import precision2dtype
 from .modules.layers import (AddContext, ContextFlashAttentionEncoderLayer, ContextFlashCrossAttentionEncoderLayer,
-                             FlashAttentionEncoderLayer, MultiRegistry, StartToken, TissueExpressionHeads, ln_fold_enabled, trunk16_enabled,
-                             packed_linear, pad_input, unpad_input)
+                             FlashAttentionEncoderLayer, MultiRegistry, StartToken, TissueExpressionHeads, _as_tensor, ln_fold_enabled,
+                             packed_linear, pad_input, trunk16_enabled, unpad_input)
 
 logger = logging.getLogger(__name__)
 MAX_WINDOW_SIZE = 30000000
@@ -260,11 +260,6 @@ def _side_stream(device, main=None):
     return _SIDE_STREAMS[key]
 
 
-def _t(x):
-    """fp32 tensor of a stream the layers may hand over as ops.LnStream (x, bf16 copy, row statistics)."""
-    return x.x if isinstance(x, ops.LnStream) else x
-
-
 def modulator_forward_packed(ctx_embedding, cre_layers, gene_layers, cre_x, gene_x, labels, cu_cre, max_cre,
                              cu_gene_self, max_gene, cu_gene_cross=None, max_gene_cross=None, cu_cre_for_gene=None,
                              final_rows=None, use_res=False, gene_unique=None):
@@ -305,7 +300,7 @@ def modulator_forward_packed(ctx_embedding, cre_layers, gene_layers, cre_x, gene
         gene = gene_layers[0].forward_packed(gene, cu_gene_self, max_gene, context=cre, cu_ctx=ck, max_ctx=max_cre,
                                              cu_cross_q=cq, max_cross_q=mq, keep_x=not t16 or use_res or n == 1, **kw0)
     if use_res:                                     # gene-stream input added back after every gene layer (:253-254)
-        gene = ops.add_rows(_t(gene), gene_x)
+        gene = ops.add_rows(_as_tensor(gene), gene_x)
     log2c = None
     if (ctx_embedding is not None and n > 1 and runtime.switches().counted_context_keys and ctx_embedding.num_embeddings <= 16
             and cre_layers[0].crossMHA.MHA.head_dim in (32, 48, 64)):
@@ -338,7 +333,7 @@ def modulator_forward_packed(ctx_embedding, cre_layers, gene_layers, cre_x, gene
             g = gene_layers[i].forward_packed(gene_in, cu_gene_self, max_gene, context=cre_i, cu_ctx=ck, max_ctx=max_cre,
                                               cu_cross_q=cq, max_cross_q=mq, keep_x=not t16 or use_res or i == n - 1)
             if use_res:                                 # :284-285
-                g = ops.add_rows(_t(g), gene_x)
+                g = ops.add_rows(_as_tensor(g), gene_x)
             return g
 
     # runtime.Switches.overlap_cre_stream (default on): the CRE layers on a SIDE STREAM beside the gene layers -- CRE layer i + 1
@@ -348,13 +343,13 @@ def modulator_forward_packed(ctx_embedding, cre_layers, gene_layers, cre_x, gene
     # run to run (tests/test_model_gpu.py), since the library has no packed-fp32 instruction (csrc/build.py).  A per-weights
     # cache a forward has to build is built on the main stream with the two streams joined (weights.build_streams).  Single
     # stream inside an ops.KernelTimer replay (per-kernel times must not depend on a neighbour).
-    overlap = runtime.switches().overlap_cre_stream and n > 2 and ops.TIMER is None and _t(cre_x).is_cuda
+    overlap = runtime.switches().overlap_cre_stream and n > 2 and ops.TIMER is None and _as_tensor(cre_x).is_cuda
     if not overlap:
         for i in range(n - 1):
             cre = cre_layer(i, cre)
             gene = gene_layer(i + 1, gene, cre)
-        return _t(gene), _t(cre)
-    dev = _t(cre_x).device
+        return _as_tensor(gene), _as_tensor(cre)
+    dev = _as_tensor(cre_x).device
     main = torch.cuda.current_stream(dev)
     side = _side_stream(dev, main)
 
@@ -390,7 +385,7 @@ def modulator_forward_packed(ctx_embedding, cre_layers, gene_layers, cre_x, gene
     ops._alert_flag(dev).bitwise_or_(side_flag)          # the side stream's LayerNorm-fold alerts belong to this batch too
     side_flag.zero_()
     side.wait_stream(main)
-    return _t(gene), _t(cre)
+    return _as_tensor(gene), _as_tensor(cre)
 
 
 class CombinedModulator(nn.Module):

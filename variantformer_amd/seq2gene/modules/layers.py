@@ -128,7 +128,7 @@ def ln_fold_enabled(*widths: int) -> bool:
             and runtime.env().ln_fold)
 
 
-def trunk16_enabled(stack: str = "modulator") -> bool:
+def trunk16_enabled() -> bool:
     """A layer's OUTPUT (the trunk: W2.h + layer input) travels to the next layer of its stack as 16-bit copies + row
     statistics only, no fp32 rows in either direction; the LAST layer of a stack (its output is pooled / returned, not fed
     to a LayerNorm -> Linear pair) keeps its fp32 result.  Part of the LayerNorm fold.  VF_TRUNK16 selects what the next
@@ -157,31 +157,100 @@ def trunk_f16_active() -> bool:
     return trunk16_mode() == "f16" and ops.cdt() == torch.bfloat16
 
 
-def down_projection(hg, w2, b2, s, keep_x: bool = True, need_t16: bool | None = None):
-    """The layer's output stream x = linear_geglu_2(hg) + (layer input s) with its 16-bit copy and row statistics
-    (LayerNorm fold).  The residual is, in this order: the fp16 trunk copy of the layer input (trunk_f16_active: taken
-    from the stream, or made from its fp32 rows for the first layer of a stack -- EVERY layer of a folded stack then adds
-    fp16(x_in * 2^-4) * 2^4, oracle.Rounding.trunk), its fp32 rows, or its operand-type copy (trunk16 modes "s2r" / "1").
-    keep_x: store the fp32 rows (the last layer of a stack); otherwise the next layer reads the copies only."""
-    if trunk_f16_active():
-        t = s.t16 if s.t16 is not None else ops.trunk16_of(s.x)
-        return ops.gemm_ln_producer(hg, w2, b2, None, need_x=keep_x, trunk16=t,
-                                    need_t16=(not keep_x) if need_t16 is None else need_t16)
-    return ops.gemm_ln_producer(hg, w2, b2, _ffn_residual(s), need_x=keep_x)
-
-
-def _ffn_residual(s):
-    """The layer input as the residual of the down-projection: its fp32 rows when they exist (the first layer of a stack,
-    or VF_TRUNK16=0), else the stream itself = its 16-bit copy."""
-    return s.x if s.x is not None else s
-
-
 def _as_stream(x):
     return x if isinstance(x, ops.LnStream) else ops.ln_stream(x)
 
 
 def _as_tensor(x):
     return x.x if isinstance(x, ops.LnStream) else x
+
+
+# ---------------------------------------------------------------------------------------------
+# The blocks every transformer layer is a sequence of.  Each takes "the stream" in the form the layer runs in -- an
+# ops.LnStream when LayerNorm is folded into the GEMMs (ln_fold_enabled), fp32 rows when it is a pass of its own -- and does
+# its one thing in that form.  A layer decides the form once per call (layer_streams) and never names it again.
+# ---------------------------------------------------------------------------------------------
+def layer_streams(layer, src, context=None):
+    """(src, context) as the blocks of `layer` take them in this call: src as an ops.LnStream when the layer runs folded
+    (its 16-bit copy and row statistics made here if no GEMM produced them; the context is taken as it comes,
+    MHA.project_kv_of), else the fp32 rows of both.  Decided per call from runtime.env() / ops.cdt(): the self-healing
+    recomputation flips it between two forwards of one model."""
+    if ln_fold_enabled(layer.norm1.weight.numel(), layer.linear_geglu_2.in_features):
+        return _as_stream(src), context
+    return _as_tensor(src), _as_tensor(context)
+
+
+def normalise(x, norm: nn.LayerNorm):
+    """LayerNorm(x) as ln_linear's operand: the 16-bit normalised rows of an fp32 stream (the separate pass); a folded stream
+    is its own operand.  For a LayerNorm whose result feeds several GEMMs (forward_packed_rows): normalised once."""
+    return x if isinstance(x, ops.LnStream) else ops.layernorm(x, norm.weight, norm.bias)
+
+
+def ln_linear(x, norm, lin: nn.Linear, epilogue: int = ops.EPI_BF16, geglu: bool = False, wscale: float = 1.0, qrows: int = 0,
+              out_rows: slice | None = None, family: str = "") -> torch.Tensor:
+    """epilogue(Linear(LayerNorm(x))).  x: an ops.LnStream -- `norm` folded into the GEMM (packed_linear_ln +
+    ops.gemm_ln_consumer); fp32 rows -- the LayerNorm pass, then the plain GEMM; a 16-bit tensor -- rows that are
+    normalised already (normalise), or that the projection takes as they are (norm None).  Only the packed form that is
+    launched is fetched: both live in the Linear's one cache slot.  geglu / wscale / qrows as in packed_linear (wscale
+    scales weights AND bias: the projection itself is scaled); out_rows: only these output rows of the Linear."""
+    cut = (lambda t: t) if out_rows is None else (lambda t: None if t is None else t[out_rows])
+    if isinstance(x, ops.LnStream):
+        w, b, c = packed_linear_ln(lin, norm, geglu=geglu, wscale=wscale, qrows=qrows)
+        return ops.gemm_ln_consumer(x, cut(w), cut(b), cut(c), epilogue, family=family)
+    h = normalise(x, norm) if x.dtype == torch.float32 else x
+    w, b = packed_linear(lin, geglu=geglu, wscale=wscale, bscale=wscale, qrows=qrows)
+    return ops.gemm(h, cut(w), cut(b), epilogue, family=family)
+
+
+def out_residual(a, w, b, x):
+    """a . w^T + b + x as the next block's stream, x being the stream the block read: folded, the sum travels as 16-bit copy
+    + statistics with x's 16-BIT COPY as the residual and no fp32 rows (the attention-block sums x1 = out_proj(attn) + src,
+    x2 = out_proj(cross) + x1 are read only through the next LayerNorm -> Linear pair and as the next block's residual, both
+    in 16 bits: DESIGN.md section 3 item 9; oracle.Rounding(res16=True) -- the layers add their FFN to the layer INPUT,
+    reference layers.py:99,163 / seq2reg/modules.py:188, so these sums have no other reader); else fp32 rows, the add in
+    the GEMM epilogue."""
+    if isinstance(x, ops.LnStream):
+        return ops.gemm_ln_producer(a, w, b, x, need_x=False)
+    return ops.gemm(a, w, b, ops.EPI_RES_F32, residual=x)
+
+
+def down_projection(hg, lin: nn.Linear, s, keep_x: bool = True, rows32: bool = False, pooled=None):
+    """The layer's output lin(hg) + (layer input s), and the ONE place that chooses the operand the layer input is added
+    as.  s folded: in this order, the fp16 trunk copy of the layer input (trunk_f16_active: taken from the stream, or made
+    from its fp32 rows for the first layer of a stack -- EVERY layer of a folded stack then adds fp16(x_in * 2^-4) * 2^4,
+    oracle.Rounding.trunk), its fp32 rows when they exist (the first layer of a stack, or VF_TRUNK16=0), else its 16-bit
+    operand copy.  The result is an ops.LnStream (16-bit copy, row statistics, and the fp16 trunk copy when the fp32 rows
+    are not kept) -- keep_x: store its fp32 rows (the last layer of a stack); otherwise the next layer reads the copies only.
+    s fp32 rows (separate LayerNorm): fp32 rows, the add in the GEMM epilogue.
+    rows32: the caller wants plain fp32 rows whatever the form (the tokenizer's last layer feeds the pooling, the registry
+    rows the heads; not a LayerNorm): no statistics are made where the fp32 rows of s serve as the residual.
+    pooled(hg, w2, b2, res_f32=None | res16=, res16_scale=): the down-projection is evaluated by the caller on pooled rows
+    (FlashTransformerLayer._pooled_down_projection) with the very residual operand the token-level form would add."""
+    w2, b2 = packed_linear(lin)
+    folded = isinstance(s, ops.LnStream)
+    t16 = None
+    if folded and trunk_f16_active():
+        t16 = s.t16 if s.t16 is not None else ops.trunk16_of(s.x)
+    x32 = s.x if folded else s              # None: a folded stream that travels without fp32 rows
+    if pooled is not None:
+        if t16 is not None:
+            return pooled(hg, w2, b2, res16=t16, res16_scale=1.0 / ops.T16_SCALE)
+        return pooled(hg, w2, b2, res_f32=x32) if x32 is not None else pooled(hg, w2, b2, res16=s.x16, res16_scale=1.0 / s.scale)
+    if t16 is None and x32 is not None and (rows32 or not folded):
+        return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=x32)
+    need_x = keep_x or rows32
+    if t16 is not None:
+        out = ops.gemm_ln_producer(hg, w2, b2, None, need_x=need_x, trunk16=t16, need_t16=not need_x)
+    else:
+        out = ops.gemm_ln_producer(hg, w2, b2, s if x32 is None else x32, need_x=need_x)
+    return out.x if rows32 else out
+
+
+def feed_forward(x, norm, layer, s, **how):
+    """The tail of every layer: LayerNorm -> linear_geglu_1 (GeGLU, one GEMM epilogue on the row-interleaved weights) ->
+    linear_geglu_2 + layer input s (down_projection, which takes `how`)."""
+    hg = ln_linear(x, norm, layer.linear_geglu_1, ops.EPI_GEGLU_BF16, geglu=True)
+    return down_projection(hg, layer.linear_geglu_2, s, **how)
 
 
 def _cu_from_padded(batch: int, seqlen: int, device) -> torch.Tensor:
@@ -215,7 +284,7 @@ class MHA(nn.Module):
 
     __call__(x[, x_kv], cu_seqlens=, max_seqlen=, cu_seqlens_k=, max_seqlen_k=) on packed [tokens, D]
     (or padded [B,S,D] with no kwargs) returns out_proj(attention) in x's dtype, like the original.
-    The layers use `fused()` which also folds the residual add into the out_proj epilogue."""
+    The layers use self_block / cross_block, which also fold the residual add into the out_proj epilogue."""
 
     def __init__(self, embed_dim, num_heads, dropout=0.0, use_flash_attn=True, use_alibi=False, cross_attn=False, **kw):
         super().__init__()
@@ -236,17 +305,17 @@ class MHA(nn.Module):
         else:
             self.alibi_slopes = None
 
-    def packed_qkv(self):
-        """packed_linear(Wqkv) with the Q rows carrying the base-2 softmax scale 1 / sqrt(dh) * log2(e): q . k leaves the
-        matrix pipe as the base-2 logit (ops.attn_varlen(q_log2=True)) -- one rounding of the scaled weights instead of one of the
-        unscaled ones; oracle.Rounding(q_prescale=...) restates the rounding point.  What it buys: the long-stream attention
-        kernel drops the running maximum and the multiply-add in front of every exponential (gene -> CRE cross attention -14 %)."""
-        c = self.q_log2_scale
-        return packed_linear(self.Wqkv, wscale=c, bscale=c, qrows=self.embed_dim)
+    def project_qkv(self, x, norm, out_rows: slice | None = None, family: str = "") -> torch.Tensor:
+        """16-bit [tokens, 3D] = Wqkv(LayerNorm(x)) (ln_linear: x in either LayerNorm form, or normalised already) with the Q
+        rows carrying the base-2 softmax scale 1 / sqrt(dh) * log2(e): q . k leaves the matrix pipe as the base-2 logit
+        (ops.attn_varlen(q_log2=True)) -- one rounding of the scaled weights instead of one of the unscaled ones;
+        oracle.Rounding(q_prescale=...) restates the rounding point.  What it buys: the long-stream attention kernel drops
+        the running maximum and the multiply-add in front of every exponential (gene -> CRE cross attention -14 %)."""
+        return ln_linear(x, norm, self.Wqkv, wscale=self.q_log2_scale, qrows=self.embed_dim, out_rows=out_rows, family=family)
 
-    def packed_qkv_ln(self, norm: nn.LayerNorm):
-        """packed_linear_ln(Wqkv, norm), Q rows as in packed_qkv."""
-        return packed_linear_ln(self.Wqkv, norm, wscale=self.q_log2_scale, qrows=self.embed_dim)
+    def project_q(self, x, norm) -> torch.Tensor:
+        """16-bit [tokens, D] = Wq(LayerNorm(x)), the whole projection carrying the base-2 softmax scale (project_qkv)."""
+        return ln_linear(x, norm, self.Wq, wscale=self.q_log2_scale)
 
     # -- pieces -------------------------------------------------------------------------------
     def project_kv(self, x_kv_bf16: torch.Tensor) -> torch.Tensor:
@@ -255,40 +324,24 @@ class MHA(nn.Module):
         return ops.gemm(x_kv_bf16, w, b, ops.EPI_BF16)
 
     def project_kv_of(self, ctx) -> torch.Tensor:
-        """project_kv of a context stream: an fp32 tensor (cast here), or an ops.LnStream, whose 16-bit copy is the
+        """project_kv of a context stream: a tensor (fp32: cast here), or an ops.LnStream, whose 16-bit copy is the
         operand -- un-normalised use, so a SCALED copy (fp16 mode) meets weights scaled by the inverse power of two:
         (x * s) . (W / s) = x . W in the fp32 accumulator, with the mantissas of fp16(x) and fp16(W)."""
         if not isinstance(ctx, ops.LnStream):
-            return self.project_kv(ops.cast16(ctx))
+            return self.project_kv(ops.cast16(ctx) if ctx.dtype == torch.float32 else ctx)
         if ctx.scale == 1.0:
             return self.project_kv(ctx.x16)
         w, b = packed_linear(self.Wkv, wscale=1.0 / ctx.scale)
         return ops.gemm(ctx.x16, w, b, ops.EPI_BF16)
 
-    def attend(self, x_bf16, kv_bf16, cu_q, max_q, cu_k, max_k) -> torch.Tensor:
-        """bf16 attention output [tokens_q, D] (before out_proj)."""
+    def attend(self, x, norm, kv_bf16, cu_q, max_q, cu_k=None, max_k=None) -> torch.Tensor:
+        """16-bit attention output [tokens_q, D] (before out_proj) of LayerNorm(x); x, norm as ln_linear takes them (norm
+        None: x is the 16-bit operand itself)."""
         D = self.embed_dim
         if self.cross_attn:
-            c = self.q_log2_scale                                    # q carries the base-2 softmax scale
-            w, b = packed_linear(self.Wq, wscale=c, bscale=c)
-            q = ops.gemm(x_bf16, w, b, ops.EPI_BF16)
-            return ops.attn_varlen(q, kv_bf16[:, :D], kv_bf16[:, D:], cu_q, cu_k, max_q, max_k, self.num_heads,
-                                   self.head_dim, self.alibi_slopes, family=self.family, q_log2=True)
-        w, b = self.packed_qkv()
-        qkv = ops.gemm(x_bf16, w, b, ops.EPI_BF16)
-        return self.attend_qkv(qkv, cu_q, max_q)
-
-    def attend_ln(self, s: "ops.LnStream", norm: nn.LayerNorm, kv_bf16, cu_q, max_q, cu_k, max_k) -> torch.Tensor:
-        """attend(LayerNorm(s.x)) with the LayerNorm folded into the Wqkv / Wq projection."""
-        D = self.embed_dim
-        if self.cross_attn:
-            w, b, c = packed_linear_ln(self.Wq, norm, wscale=self.q_log2_scale)
-            q = ops.gemm_ln_consumer(s, w, b, c, ops.EPI_BF16)
-            return ops.attn_varlen(q, kv_bf16[:, :D], kv_bf16[:, D:], cu_q, cu_k, max_q, max_k, self.num_heads,
-                                   self.head_dim, self.alibi_slopes, family=self.family, q_log2=True)
-        w, b, c = self.packed_qkv_ln(norm)
-        qkv = ops.gemm_ln_consumer(s, w, b, c, ops.EPI_BF16)
-        return self.attend_qkv(qkv, cu_q, max_q)
+            return ops.attn_varlen(self.project_q(x, norm), kv_bf16[:, :D], kv_bf16[:, D:], cu_q, cu_k, max_q, max_k,
+                                   self.num_heads, self.head_dim, self.alibi_slopes, family=self.family, q_log2=True)
+        return self.attend_qkv(self.project_qkv(x, norm), cu_q, max_q)
 
     def lowrank_tables(self, norm, table: torch.Tensor):
         """Weights of the LOW-RANK form of a cross attention whose keys / values are Wkv of the C rows of `table` (fp32 [C, D]):
@@ -327,38 +380,29 @@ class MHA(nn.Module):
             return wz, bz, cs, u16, bo, Cp
         return weights.derived(self, "_vf_lowrank_ln" if norm is not None else "_vf_lowrank", prm, build)
 
-    def cross_lowrank(self, x, norm, table, log2_count, cu_q, max_q, residual, tables=None):
-        """out_proj(cross attention of LayerNorm(x) against Wkv(table rows), row c counted 2^log2_count[s, c] times) + residual
-        in the low-rank form (lowrank_tables): two skinny GEMMs around vf_softmax_counted.  x: an ops.LnStream (norm folded)
-        -> returns an LnStream (16-bit copy + statistics, no fp32 rows), or, norm=None, an already normalised 16-bit tensor with
-        an fp32 residual -> fp32 rows."""
-        wz, bz, cs, u16, bo, Cp = tables if tables is not None else self.lowrank_tables(norm, table)
-        if norm is not None:
-            sc = ops.gemm_ln_consumer(x, wz, bz, cs, ops.EPI_F32)
+    def cross_lowrank(self, h, tables, log2_count, cu_q, max_q, x):
+        """out_proj(cross attention of LayerNorm(x) against Wkv(table rows), row c counted 2^log2_count[s, c] times) + x in
+        the low-rank form: two skinny GEMMs around vf_softmax_counted.  tables = lowrank_tables(norm, table), with the norm
+        when x is folded; h = normalise(x, norm); the sum comes back as out_residual's."""
+        wz, bz, cs, u16, bo, Cp = tables
+        if isinstance(h, ops.LnStream):
+            sc = ops.gemm_ln_consumer(h, wz, bz, cs, ops.EPI_F32)
         else:
-            sc = ops.gemm(x, wz, bz, ops.EPI_F32)
+            sc = ops.gemm(h, wz, bz, ops.EPI_F32)
         w16 = ops.softmax_counted(sc, log2_count, cu_q, max_q, self.num_heads, Cp, family=self.family)
-        if norm is not None:
-            return ops.gemm_ln_producer(w16, u16, bo, residual, need_x=False)
-        return ops.gemm(w16, u16, bo, ops.EPI_RES_F32, residual=residual)
+        return out_residual(w16, u16, bo, x)
 
     def attend_counted(self, x, norm, counted, cu_q, max_q) -> torch.Tensor:
-        """Cross attention of LayerNorm(x) (x: an ops.LnStream with `norm` folded into Wq, or, norm=None, an already
-        normalised 16-bit tensor) against keys that are copies of a few distinct rows: counted = (kv_table 16-bit [C, 2D],
-        log2_count fp32 [n_seq, C]) -- ops.attn_counted_keys."""
+        """Cross attention of LayerNorm(x) (x, norm as ln_linear takes them) against keys that are copies of a few distinct
+        rows: counted = (kv_table 16-bit [C, 2D], log2_count fp32 [n_seq, C]) -- ops.attn_counted_keys.  q always carries
+        the base-2 softmax scale here."""
         assert self.cross_attn and self.alibi_slopes is None
-        c = self.q_log2_scale                                    # q always carries the base-2 softmax scale here
-        if norm is not None:
-            w, b, cs = packed_linear_ln(self.Wq, norm, wscale=c)
-            q = ops.gemm_ln_consumer(x, w, b, cs, ops.EPI_BF16)
-        else:
-            w, b = packed_linear(self.Wq, wscale=c, bscale=c)
-            q = ops.gemm(x, w, b, ops.EPI_BF16)
-        return ops.attn_counted_keys(q, counted[0], counted[1], cu_q, max_q, self.num_heads, self.head_dim, family=self.family)
+        return ops.attn_counted_keys(self.project_q(x, norm), counted[0], counted[1], cu_q, max_q, self.num_heads, self.head_dim,
+                                     family=self.family)
 
     def attend_qkv(self, qkv, cu_q, max_q, rows=None) -> torch.Tensor:
-        """self attention on a packed [tokens, 3D] 16-bit projection (rows ordered (three, head, dh)) made with packed_qkv /
-        packed_qkv_ln (its Q third carries the base-2 softmax scale).
+        """self attention on a packed [tokens, 3D] 16-bit projection (rows ordered (three, head, dh)) made with project_qkv
+        (its Q third carries the base-2 softmax scale).
         rows int64 [tokens]: qkv is a TABLE of distinct projected rows and token t's row is rows[t] (the first layers'
         projection by lookup): the attention kernel gathers in its loads where it can (ops.attn_rows_supported); otherwise
         the rows are gathered first -- the same bits either way."""
@@ -370,22 +414,36 @@ class MHA(nn.Module):
                                self.num_heads, self.head_dim, self.alibi_slopes, family=self.family,
                                q_log2=True, rows=rows)
 
-    def out_ln(self, a_bf16, residual_f32, need_x: bool = True) -> "ops.LnStream":
-        """out_proj(a) + residual as an LnStream (fp32 stream, its 16-bit copy, row statistics for the next LayerNorm).
-        `residual_f32`: the fp32 rows, or an LnStream whose 16-bit copy is the residual (the attention-block sums
-        x1 = out_proj(attn) + src, x2 = out_proj(cross) + x1 are read only through the next LayerNorm -> Linear pair and as
-        the next block's residual, both in 16 bits: DESIGN.md section 3 item 9; oracle.Rounding(res16=True)).
-        need_x=False when the sum is only ever read through the next LayerNorm -> Linear pair (the layers add their FFN
-        to the layer INPUT, reference layers.py:99,163 / seq2reg/modules.py:188, so the stream after the last attention
-        block has no other reader): the fp32 values are then not written to HBM at all."""
+    def out_proj_residual(self, a, x):
+        """out_proj(a) + x as the next block's stream (out_residual)."""
         w, b = packed_linear(self.out_proj)
-        return ops.gemm_ln_producer(a_bf16, w, b, residual_f32, need_x=need_x)
+        return out_residual(a, w, b, x)
 
-    def fused(self, x_bf16, residual_f32, cu_q, max_q, kv_bf16=None, cu_k=None, max_k=None) -> torch.Tensor:
-        """fp32 [tokens, D] = out_proj(attention(x)) + residual (one GEMM epilogue)."""
-        a = self.attend(x_bf16, kv_bf16, cu_q, max_q, cu_k, max_k)
-        w, b = packed_linear(self.out_proj)
-        return ops.gemm(a, w, b, ops.EPI_RES_F32, residual=residual_f32)
+    def self_block(self, x, norm, cu, max_len, qkv=None):
+        """out_proj(self attention of LayerNorm(x)) + x.  qkv = (table, row per token): the project_qkv projection, already
+        made on the distinct rows of x (the first layer of a stack); only the residual reads the stream then."""
+        a = self.attend(x, norm, None, cu, max_len) if qkv is None else self.attend_qkv(qkv[0], cu, max_len, rows=qkv[1])
+        return self.out_proj_residual(a, x)
+
+    def cross_block(self, x, norm, cu_q, max_q, context=None, cu_k=None, max_k=None, context_kv=None, context_counted=None):
+        """out_proj(cross attention of LayerNorm(x) against the un-normalised context) + x, and the ONE place that picks
+        where the keys / values come from: context_counted = (kv_table [C, 2D], log2_count [n_seq, C][, table fp32 [C, D]])
+        -- the context rows are copies of C distinct rows: the low-rank form when the raw table is given and has one
+        (cross_lowrank: two skinny GEMMs around a 9-way softmax), else attend_counted; context_kv -- a precomputed 16-bit
+        [tokens_k, 2D]; context -- a stream, projected here (project_kv_of)."""
+        h = normalise(x, norm)
+        lr = None
+        if context_counted is not None and runtime.switches().lowrank_context and len(context_counted) > 2:
+            lr = self.lowrank_tables(norm if isinstance(x, ops.LnStream) else None, context_counted[2])
+        if lr is not None:
+            return self.cross_lowrank(h, lr, context_counted[1], cu_q, max_q, x)
+        if context_counted is not None:
+            a = self.attend_counted(h, norm, context_counted, cu_q, max_q)
+        else:
+            if context_kv is None:
+                context_kv = self.project_kv_of(context)
+            a = self.attend(h, norm, context_kv, cu_q, max_q, cu_k, max_k)
+        return self.out_proj_residual(a, x)
 
     # -- flash_attn-compatible call -------------------------------------------------------------
     def forward(self, x, x_kv=None, cu_seqlens=None, max_seqlen=None, cu_seqlens_k=None, max_seqlen_k=None, **kw):
@@ -410,7 +468,7 @@ class MHA(nn.Module):
             kv = self.project_kv(src if src.dtype == cd else ops.cast16(src.float().contiguous()))
             if cu_seqlens_k is None:
                 cu_seqlens_k, max_seqlen_k = cu_seqlens, max_seqlen
-        a = self.attend(xb, kv, cu_seqlens, max_seqlen, cu_seqlens_k, max_seqlen_k)
+        a = self.attend(xb, None, kv, cu_seqlens, max_seqlen, cu_seqlens_k, max_seqlen_k)
         w, b = packed_linear(self.out_proj)
         out = ops.gemm(a, w, b, ops.EPI_F32 if in_dtype == torch.float32 else ops.EPI_BF16)
         return out.to(in_dtype).view(in_shape)
@@ -491,21 +549,20 @@ class ContextFlashAttentionEncoderLayer(nn.Module):
         layer needs fp32 rows (VF_TRUNK16=0, fp16 operands)."""
         if not ln_fold_enabled(self.norm1.weight.numel(), self.linear_geglu_2.in_features):
             return None
-        w, b, c = self.mixer.MHA.packed_qkv_ln(self.norm1)
         sa = ops.ln_stream(rows_a.float().contiguous())
-        qa = ops.gemm_ln_consumer(sa, w, b, c, ops.EPI_BF16)
+        qa = self.mixer.MHA.project_qkv(sa, self.norm1)
         tab_b = rows_b.float().contiguous()
         if rows_b_used is not None:
             ops.ln_stream(tab_b[rows_b_used].contiguous())       # statistics of the rows in use: raises the alert, result unused
         sb = ops.ln_stream(tab_b, raise_alert=rows_b_used is None)
-        qb = ops.gemm_ln_consumer(sb, w, b, c, ops.EPI_BF16)
+        qb = self.mixer.MHA.project_qkv(sb, self.norm1)
         both = torch.cat([qa, qb], dim=0)                        # (a few thousand rows: index plumbing, not data movement)
         idx2 = torch.where(idx >= 0, idx, rows_a.shape[0] - idx - 1)
         qkv = (both, idx2)           # (table of distinct projected rows, row of every token): gathered by the attention's loads
         if not with_stream:
             return qkv
         stream = None
-        if trunk16_enabled() and trunk_f16_active():
+        if trunk_f16_active():
             # (bf16 operands with the fp16 trunk copy, the default.  With fp16 operands the FIRST layer of a stack adds its fp32
             # input rows in the down-projection -- oracle.Rounding.trunk -- so that mode keeps the fp32 gather.)
             x16 = ops.gather_rows_bf16(torch.cat([sa.x16, sb.x16], dim=0), idx2)
@@ -527,60 +584,12 @@ class ContextFlashAttentionEncoderLayer(nn.Module):
         given (two skinny GEMMs around a 9-way softmax), else MHA.attend_counted."""
         if self.make_data_kv:
             return self._forward_packed_data_kv(src, cu_src, max_src, context, cu_ctx, max_ctx)
-        cq = cu_src if cu_cross_q is None else cu_cross_q
-        mq = max_src if max_cross_q is None else max_cross_q
-        if ln_fold_enabled(self.norm1.weight.numel(), self.linear_geglu_2.in_features):
-            # LayerNorm folded into the GEMMs: every fp32-residual GEMM also emits the bf16 copy + row statistics of its
-            # output, every LayerNorm -> Linear pair runs on that copy (no LayerNorm pass, no cast of the context)
-            # (the attention-block sums x1, x2 travel as 16-bit copies + statistics, no fp32 rows: section 3 item 9)
-            if self_qkv is not None:
-                # the projection was computed on the distinct rows; below only the residuals read the stream: its fp32
-                # rows / trunk copy (layer output) and its 16-bit copy (self-attention block)
-                s = _as_stream(src)
-                a = self.mixer.MHA.attend_qkv(self_qkv[0], cu_src, max_src, rows=self_qkv[1])
-            else:
-                s = _as_stream(src)
-                a = self.mixer.MHA.attend_ln(s, self.norm1, None, cu_src, max_src, None, None)
-            x1 = self.mixer.MHA.out_ln(a, s, need_x=False)
-            lr = None
-            if context_counted is not None and runtime.switches().lowrank_context and len(context_counted) > 2:
-                lr = self.crossMHA.MHA.lowrank_tables(self.norm2, context_counted[2])
-            if lr is not None:
-                x2 = self.crossMHA.MHA.cross_lowrank(x1, self.norm2, None, context_counted[1], cq, mq, x1, tables=lr)
-            else:
-                if context_counted is not None:
-                    a = self.crossMHA.MHA.attend_counted(x1, self.norm2, context_counted, cq, mq)
-                else:
-                    if context_kv is None:
-                        context_kv = self.crossMHA.MHA.project_kv_of(context)
-                    a = self.crossMHA.MHA.attend_ln(x1, self.norm2, context_kv, cq, mq, cu_ctx, max_ctx)
-                x2 = self.crossMHA.MHA.out_ln(a, x1, need_x=False)
-            w1, b1, c1 = packed_linear_ln(self.linear_geglu_1, self.norm3, geglu=True)
-            hg = ops.gemm_ln_consumer(x2, w1, b1, c1, ops.EPI_GEGLU_BF16)
-            w2, b2 = packed_linear(self.linear_geglu_2)
-            return down_projection(hg, w2, b2, s, keep_x)
-        src, context = _as_tensor(src), _as_tensor(context)
-        h = ops.layernorm(src, self.norm1.weight, self.norm1.bias)
-        x1 = self.mixer.MHA.fused(h, src, cu_src, max_src)
-        h = ops.layernorm(x1, self.norm2.weight, self.norm2.bias)
-        lr = None
-        if context_counted is not None and runtime.switches().lowrank_context and len(context_counted) > 2:
-            lr = self.crossMHA.MHA.lowrank_tables(None, context_counted[2])
-        if lr is not None:
-            x2 = self.crossMHA.MHA.cross_lowrank(h, None, None, context_counted[1], cq, mq, x1, tables=lr)
-        elif context_counted is not None:
-            a = self.crossMHA.MHA.attend_counted(h, None, context_counted, cq, mq)
-            w, b = packed_linear(self.crossMHA.MHA.out_proj)
-            x2 = ops.gemm(a, w, b, ops.EPI_RES_F32, residual=x1)
-        else:
-            if context_kv is None:
-                context_kv = self.crossMHA.MHA.project_kv(ops.cast16(context))
-            x2 = self.crossMHA.MHA.fused(h, x1, cq, mq, context_kv, cu_ctx, max_ctx)
-        h = ops.layernorm(x2, self.norm3.weight, self.norm3.bias)
-        w1, b1 = packed_linear(self.linear_geglu_1, geglu=True)
-        hg = ops.gemm(h, w1, b1, ops.EPI_GEGLU_BF16)
-        w2, b2 = packed_linear(self.linear_geglu_2)
-        return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=src)
+        s, context = layer_streams(self, src, context)
+        x1 = self.mixer.MHA.self_block(s, self.norm1, cu_src, max_src, qkv=self_qkv)
+        x2 = self.crossMHA.MHA.cross_block(x1, self.norm2, cu_src if cu_cross_q is None else cu_cross_q,
+                                           max_src if max_cross_q is None else max_cross_q, context, cu_ctx, max_ctx,
+                                           context_kv, context_counted)
+        return feed_forward(x2, self.norm3, self, s, keep_x=keep_x)
 
     def _forward_packed_data_kv(self, src, cu_src, max_src, context, cu_ctx, max_ctx):
         """make_data_kv=True (reference layers.py:133-136, seq2reg/modules.py:97-100): the roles of the two streams in the
@@ -594,16 +603,12 @@ class ContextFlashAttentionEncoderLayer(nn.Module):
                                "when they sit inside a LayerNorm-folded stack)")
         assert context.shape == src.shape and (cu_ctx is None or cu_ctx is cu_src or torch.equal(cu_ctx, cu_src)), \
             "make_data_kv: src and context must have the same shape (reference seq2reg/modules.py:79)"
-        h = ops.layernorm(src, self.norm1.weight, self.norm1.bias)
-        x1 = self.mixer.MHA.fused(h, src, cu_src, max_src)
-        h = ops.layernorm(x1, self.norm2.weight, self.norm2.bias)
-        kv = self.crossMHA.MHA.project_kv(h)                               # K / V from the NORMALISED stream
-        x2 = self.crossMHA.MHA.fused(ops.cast16(context), x1, cu_src, max_src, kv, cu_src, max_src)     # Q from the raw context
-        h = ops.layernorm(x2, self.norm3.weight, self.norm3.bias)
-        w1, b1 = packed_linear(self.linear_geglu_1, geglu=True)
-        hg = ops.gemm(h, w1, b1, ops.EPI_GEGLU_BF16)
-        w2, b2 = packed_linear(self.linear_geglu_2)
-        return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=src)
+        cross = self.crossMHA.MHA
+        x1 = self.mixer.MHA.self_block(src, self.norm1, cu_src, max_src)
+        kv = cross.project_kv(normalise(x1, self.norm2))                    # K / V from the NORMALISED stream
+        a = cross.attend(ops.cast16(context), None, kv, cu_src, max_src, cu_src, max_src)     # Q from the raw context
+        x2 = cross.out_proj_residual(a, x1)
+        return feed_forward(x2, self.norm3, self, src)
 
     def forward_packed_rows(self, src, cu_src, max_src, rows, cu_rows, context, cu_ctx, max_ctx, cu_cross_rows,
                             max_cross_rows):
@@ -615,49 +620,22 @@ class ContextFlashAttentionEncoderLayer(nn.Module):
         model_combined_modulator.py:391-392): exact, and ~1/25 of the gene-stream work less."""
         if self.make_data_kv:
             raise NotImplementedError("make_data_kv: the cross attention's rows are context rows; no registry-only form")
-        mha = self.mixer.MHA
-        if ln_fold_enabled(self.norm1.weight.numel(), self.linear_geglu_2.in_features):
-            s = _as_stream(src)
-            D = s.x16.shape[1]
-            w, b, c = mha.packed_qkv_ln(self.norm1)
-            kv = ops.gemm_ln_consumer(s, w[D:], b[D:], c[D:], ops.EPI_BF16)            # all rows (K/V need them)
-            sr = ops.ln_stream_rows(s, rows)
-            q = ops.gemm_ln_consumer(sr, w[:D], b[:D], c[:D], ops.EPI_BF16)            # [R, D]
-            a = ops.attn_varlen(q, kv[:, :D], kv[:, D:], cu_rows, cu_src, 1, max_src, mha.num_heads, mha.head_dim,
-                                mha.alibi_slopes, q_at_start=True, family=mha.family + "_registry_rows",
-                                q_log2=True)
-            x1 = mha.out_ln(a, sr, need_x=False)
-            ckv = self.crossMHA.MHA.project_kv_of(context)
-            a = self.crossMHA.MHA.attend_ln(x1, self.norm2, ckv, cu_cross_rows, max_cross_rows, cu_ctx, max_ctx)
-            x2 = self.crossMHA.MHA.out_ln(a, x1, need_x=False)
-            w1, b1, c1 = packed_linear_ln(self.linear_geglu_1, self.norm3, geglu=True)
-            hg = ops.gemm_ln_consumer(x2, w1, b1, c1, ops.EPI_GEGLU_BF16)
-            w2, b2 = packed_linear(self.linear_geglu_2)
-            if sr.x is None or trunk_f16_active():     # 16-bit trunk: the registry rows' residual is their trunk copy
-                return down_projection(hg, w2, b2, sr, keep_x=True, need_t16=False).x
-            return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=sr.x)
-        ctx16 = context.operand16() if isinstance(context, ops.LnStream) else None
-        src, context = _as_tensor(src), _as_tensor(context)
-        D = src.shape[1]
-        h = ops.layernorm(src, self.norm1.weight, self.norm1.bias)                       # all rows (K/V need them)
-        w, b = mha.packed_qkv()
-        kv = ops.gemm(h, w[D:], None if b is None else b[D:], ops.EPI_BF16)             # [tokens, 2D]
-        hq = ops.gather_rows_bf16(h, rows)
-        q = ops.gemm(hq, w[:D], None if b is None else b[:D], ops.EPI_BF16)             # [R, D]
+        mha, D = self.mixer.MHA, self.mixer.MHA.embed_dim
+        s, ctx = layer_streams(self, src, context)
+        folded = isinstance(s, ops.LnStream)
+        if isinstance(context, ops.LnStream) and not folded:
+            ctx = context.operand16()
+        h = normalise(s, self.norm1)                                               # once, for both projections
+        kv = mha.project_qkv(h, self.norm1, out_rows=slice(D, None))               # [tokens, 2D]: all rows (K/V need them)
+        hr = ops.ln_stream_rows(h, rows) if folded else ops.gather_rows_bf16(h, rows)
+        q = mha.project_qkv(hr, self.norm1, out_rows=slice(0, D))                  # [R, D]
         a = ops.attn_varlen(q, kv[:, :D], kv[:, D:], cu_rows, cu_src, 1, max_src, mha.num_heads, mha.head_dim,
                             mha.alibi_slopes, q_at_start=True, family=mha.family + "_registry_rows",
                             q_log2=True)
-        src_rows = ops.gather_rows_f32(src, None, rows)
-        wo, bo = packed_linear(mha.out_proj)
-        x1 = ops.gemm(a, wo, bo, ops.EPI_RES_F32, residual=src_rows)
-        h = ops.layernorm(x1, self.norm2.weight, self.norm2.bias)
-        ckv = self.crossMHA.MHA.project_kv(ctx16 if ctx16 is not None else ops.cast16(context))
-        x2 = self.crossMHA.MHA.fused(h, x1, cu_cross_rows, max_cross_rows, ckv, cu_ctx, max_ctx)
-        h = ops.layernorm(x2, self.norm3.weight, self.norm3.bias)
-        w1, b1 = packed_linear(self.linear_geglu_1, geglu=True)
-        hg = ops.gemm(h, w1, b1, ops.EPI_GEGLU_BF16)
-        w2, b2 = packed_linear(self.linear_geglu_2)
-        return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=src_rows)
+        sr = hr if folded else ops.gather_rows_f32(s, None, rows)                  # the selected rows of the layer input
+        x1 = mha.out_proj_residual(a, sr)
+        x2 = self.crossMHA.MHA.cross_block(x1, self.norm2, cu_cross_rows, max_cross_rows, ctx, cu_ctx, max_ctx)
+        return feed_forward(x2, self.norm3, self, sr, rows32=True)
 
     def forward(self, src, context, src_key_padding_mask=None, context_padding_mask=None, precision=torch.float32,
                 unpad_info=None, context_unpad_info=None, gene_unpad_info=None):
@@ -711,22 +689,9 @@ class FlashAttentionEncoderLayer(nn.Module):
             self.register_buffer("m", get_alibi_slopes(self.num_heads))
 
     def forward_packed(self, src, cu_src, max_src, keep_x=True, **_):
-        if ln_fold_enabled(self.norm1.weight.numel(), self.linear_geglu_2.in_features):
-            s = _as_stream(src)
-            a = self.mixer.MHA.attend_ln(s, self.norm1, None, cu_src, max_src, None, None)
-            x1 = self.mixer.MHA.out_ln(a, s, need_x=False)
-            w1, b1, c1 = packed_linear_ln(self.linear_geglu_1, self.norm2, geglu=True)
-            hg = ops.gemm_ln_consumer(x1, w1, b1, c1, ops.EPI_GEGLU_BF16)
-            w2, b2 = packed_linear(self.linear_geglu_2)
-            return down_projection(hg, w2, b2, s, keep_x)
-        src = _as_tensor(src)
-        h = ops.layernorm(src, self.norm1.weight, self.norm1.bias)
-        x1 = self.mixer.MHA.fused(h, src, cu_src, max_src)
-        h = ops.layernorm(x1, self.norm2.weight, self.norm2.bias)
-        w1, b1 = packed_linear(self.linear_geglu_1, geglu=True)
-        hg = ops.gemm(h, w1, b1, ops.EPI_GEGLU_BF16)
-        w2, b2 = packed_linear(self.linear_geglu_2)
-        return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=src)
+        s = layer_streams(self, src)[0]
+        x1 = self.mixer.MHA.self_block(s, self.norm1, cu_src, max_src)
+        return feed_forward(x1, self.norm2, self, s, keep_x=keep_x)
 
 
 class ContextFlashCrossAttentionEncoderLayer(nn.Module):
@@ -750,42 +715,20 @@ class ContextFlashCrossAttentionEncoderLayer(nn.Module):
 
     def forward_packed(self, src, cu_src, max_src, context=None, cu_ctx=None, max_ctx=None, context_kv=None,
                        cu_cross_q=None, max_cross_q=None, keep_x=True):
+        cross = self.crossMHA.MHA
         if self.make_data_kv:
             # reference layers.py:283-286: Q from the raw context, K / V from norm1(x); context and stream hold the same
             # sequences (the attention output is added to the stream).  Separate-LayerNorm path, as above.
             src, context = _as_tensor(src), _as_tensor(context)
             assert src is not None and context is not None and context.shape == src.shape, \
                 "make_data_kv: src and context must have the same shape"
-            h = ops.layernorm(src, self.norm1.weight, self.norm1.bias)
-            kv = self.crossMHA.MHA.project_kv(h)
-            x1 = self.crossMHA.MHA.fused(ops.cast16(context), src, cu_src, max_src, kv, cu_src, max_src)
-            h = ops.layernorm(x1, self.norm2.weight, self.norm2.bias)
-            w1, b1 = packed_linear(self.linear_geglu_1, geglu=True)
-            hg = ops.gemm(h, w1, b1, ops.EPI_GEGLU_BF16)
-            w2, b2 = packed_linear(self.linear_geglu_2)
-            return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=src)
-        cq = cu_src if cu_cross_q is None else cu_cross_q
-        mq = max_src if max_cross_q is None else max_cross_q
-        if ln_fold_enabled(self.norm1.weight.numel(), self.linear_geglu_2.in_features):
-            s = _as_stream(src)
-            if context_kv is None:
-                context_kv = self.crossMHA.MHA.project_kv_of(context)
-            a = self.crossMHA.MHA.attend_ln(s, self.norm1, context_kv, cq, mq, cu_ctx, max_ctx)
-            x1 = self.crossMHA.MHA.out_ln(a, s, need_x=False)
-            w1, b1, c1 = packed_linear_ln(self.linear_geglu_1, self.norm2, geglu=True)
-            hg = ops.gemm_ln_consumer(x1, w1, b1, c1, ops.EPI_GEGLU_BF16)
-            w2, b2 = packed_linear(self.linear_geglu_2)
-            return down_projection(hg, w2, b2, s, keep_x)
-        src, context = _as_tensor(src), _as_tensor(context)
-        h = ops.layernorm(src, self.norm1.weight, self.norm1.bias)
-        if context_kv is None:
-            context_kv = self.crossMHA.MHA.project_kv(ops.cast16(context))
-        x1 = self.crossMHA.MHA.fused(h, src, cq, mq, context_kv, cu_ctx, max_ctx)
-        h = ops.layernorm(x1, self.norm2.weight, self.norm2.bias)
-        w1, b1 = packed_linear(self.linear_geglu_1, geglu=True)
-        hg = ops.gemm(h, w1, b1, ops.EPI_GEGLU_BF16)
-        w2, b2 = packed_linear(self.linear_geglu_2)
-        return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=src)
+            kv = cross.project_kv(normalise(src, self.norm1))
+            a = cross.attend(ops.cast16(context), None, kv, cu_src, max_src, cu_src, max_src)
+            return feed_forward(cross.out_proj_residual(a, src), self.norm2, self, src)
+        s, context = layer_streams(self, src, context)
+        x1 = cross.cross_block(s, self.norm1, cu_src if cu_cross_q is None else cu_cross_q,
+                               max_src if max_cross_q is None else max_cross_q, context, cu_ctx, max_ctx, context_kv)
+        return feed_forward(x1, self.norm2, self, s, keep_x=keep_x)
 
 
 class StartToken(nn.Module):

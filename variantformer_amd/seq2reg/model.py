@@ -15,6 +15,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops, runtime, weights
+from ..seq2gene.modules.layers import ContextFlashAttentionEncoderLayer, ln_fold_enabled, trunk16_enabled, trunk_f16_active
+from ..utils.constants import REF_CREs
 from .modules import FlashTransformerLayer
 
 
@@ -69,7 +71,6 @@ class Seq2RegPredictor(nn.Module):
         self.tissues = tissues
         use_alibi = positional_encoding == "alibi"
         if use_context:                       # reference seq2reg/model.py:90-95
-            from ..utils.constants import REF_CREs
             self.context_embedding = nn.Embedding(len(REF_CREs), embedding_dim)
             if expand_context:
                 self.expand_context = nn.Linear(1, token_length)
@@ -81,7 +82,6 @@ class Seq2RegPredictor(nn.Module):
             # same module tree as the reference's seq2reg ContextFlashAttentionEncoderLayer (seq2reg/modules.py:40-126):
             # mixer.MHA / crossMHA.MHA / norm1-3 / linear_geglu_1-2 / buffer m -- and the same arithmetic as the seq2gene
             # layer of that name (cross attention without ALiBi, q = tokens, k/v = the context rows)
-            from ..seq2gene.modules.layers import ContextFlashAttentionEncoderLayer
             self.transformer_encoder = nn.ModuleList(
                 [ContextFlashAttentionEncoderLayer(d_model=embedding_dim, nhead=num_heads, batch_first=True,
                                                    use_alibi=use_alibi, mlp_dout=mlp_dout) for _ in range(num_layers)])
@@ -104,7 +104,7 @@ class Seq2RegPredictor(nn.Module):
         return self._pe_dev
 
     def _layer0_qkv_table(self, device):
-        """16-bit [vocab * key_L, 3 d]: the first layer's packed_qkv_ln(norm1) projection of EVERY possible encoder input row
+        """16-bit [vocab * key_L, 3 d]: the first layer's MHA.project_qkv(norm1) projection of EVERY possible encoder input row
         x0 = Embedding(id) + positional(position) (key = id * key_L + position; key_L = token_length, or 1 with ALiBi).  The
         rows are made by the same kernels the tokens would go through (vf_embed_stream on the identity window list, then the
         LayerNorm-consumer GEMM), and a GEMM row depends on nothing but its own input row: looking a token's projection up
@@ -131,8 +131,7 @@ class Seq2RegPredictor(nn.Module):
             before = alert.clone()
             s = ops.embed_stream(ids, pad, cu, self.token_embedding.weight, pos, V * key_L, need_t16=False)
             alert.copy_(before)
-            w, b, c = l0.MHA.packed_qkv_ln(l0.norm1)
-            return ops.gemm_ln_consumer(s, w, b, c, ops.EPI_BF16, family="seq2reg")
+            return l0.MHA.project_qkv(s, l0.norm1, family="seq2reg")
         return weights.derived(self, _LAYER0_SLOTS[ops.cdt()], prm, build, key_L), key_L
 
     def _layer0_qkv_table_bytes(self) -> int:
@@ -156,7 +155,6 @@ class Seq2RegPredictor(nn.Module):
         Lmax = max_len if 0 < max_len < L else L
         with ops.scope("seq2reg"):
             cu = ops.mask_to_cu_seqlens(pad)
-            from ..seq2gene.modules.layers import ln_fold_enabled, trunk_f16_active
             l0 = self.transformer_encoder[0]
             # (vf_embed_stream serves d <= 2048; wider tokenizers keep the embed_pack + ln_stream form, which has no limit)
             if (trunk_f16_active() and ln_fold_enabled(l0.norm1.weight.numel(), l0.linear_geglu_2.in_features)
@@ -171,13 +169,11 @@ class Seq2RegPredictor(nn.Module):
                         "a use_context tokenizer needs integer cCRE labels as context; the gene branch of the reference "
                         "passes a float zero tensor (model_combined_modulator.py:575-577), which nn.Embedding rejects there too")
                 ctx = self._context_rows(pad, cu, context.to(ids.device).long().reshape(-1), n_tokens)
-                from ..seq2gene.modules.layers import trunk16_enabled
                 n_layers = len(self.transformer_encoder)
                 for li, layer in enumerate(self.transformer_encoder):
                     x = layer.forward_packed(x, cu, Lmax, context=ctx, cu_ctx=cu, max_ctx=Lmax,
-                                             keep_x=not trunk16_enabled("seq2reg") or li + 1 == n_layers)
+                                             keep_x=not trunk16_enabled() or li + 1 == n_layers)
             else:
-                from ..seq2gene.modules.layers import trunk16_enabled
                 n_layers = len(self.transformer_encoder)
                 # mean pool: the last layer returns the pooled rows themselves (its down-projection commutes with the mean)
                 lg2 = self.transformer_encoder[-1].linear_geglu_2                 # (vf_segment_mean16 serves widths <= 2048)
@@ -191,7 +187,7 @@ class Seq2RegPredictor(nn.Module):
                     tab, key_L = self._layer0_qkv_table(ids.device)
                     qkv0 = (tab, ops.token_keys(ids, pad, cu, n_tokens, V, key_L))      # gathered by the attention kernel's loads
                 for li, layer in enumerate(self.transformer_encoder):
-                    x = layer.forward_packed(x, cu, Lmax, last=li + 1 == n_layers, keep_x=not trunk16_enabled("seq2reg"),
+                    x = layer.forward_packed(x, cu, Lmax, last=li + 1 == n_layers, keep_x=not trunk16_enabled(),
                                              pool_mean=pool_in_layer and li + 1 == n_layers, qkv=qkv0 if li == 0 else None)
                 if pool_in_layer:
                     od = ops.cdt() if out_dtype is None else out_dtype

@@ -5,7 +5,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops, weights
-from ..seq2gene.modules.layers import MHA, get_alibi_slopes, packed_linear  # noqa: F401
+from ..seq2gene.modules.layers import (MHA, _as_tensor, _cu_from_padded, feed_forward, get_alibi_slopes,  # noqa: F401
+                                       layer_streams, packed_linear, pad_input, unpad_input)
 
 
 class FlashTransformerLayer(nn.Module):
@@ -47,47 +48,21 @@ class FlashTransformerLayer(nn.Module):
         the GEMMs, see seq2gene.modules.layers.ln_fold_enabled; a plain tensor from the `last` layer).  keep_x=False: the
         result's fp32 rows have no reader (16-bit trunk, layers.trunk16_enabled) and are not stored.
         pool_mean (with last): return the per-window MEAN of the layer's output rows, fp32 [W, d], instead of the rows
-        (_pooled_down_projection).  qkv (folded path): this layer's packed_qkv_ln projection of norm1(src), already made
+        (_pooled_down_projection).  qkv (folded path): this layer's MHA.project_qkv projection of norm1(src), already made
         (the encoder's first layer looks it up per distinct input row: (table, row per token) of Seq2RegPredictor._layer0_qkv_table)."""
-        from ..seq2gene.modules.layers import (_as_stream, _as_tensor, down_projection, ln_fold_enabled, packed_linear_ln,
-                                               trunk_f16_active)
-        if ln_fold_enabled(self.norm1.weight.numel(), self.linear_geglu_2.in_features):
-            s = _as_stream(src)
-            a = self.MHA.attend_ln(s, self.norm1, None, cu, max_seqlen, None, None) if qkv is None else \
-                self.MHA.attend_qkv(qkv[0], cu, max_seqlen, rows=qkv[1])
-            # x1 is read only through norm2 -> linear_geglu_1: no fp32 store, and its residual is the 16-bit copy of the input
-            x1 = self.MHA.out_ln(a, s, need_x=False)
-            w1, b1, c1 = packed_linear_ln(self.linear_geglu_1, self.norm2, geglu=True)
-            hg = ops.gemm_ln_consumer(x1, w1, b1, c1, ops.EPI_GEGLU_BF16)
-            w2, b2 = packed_linear(self.linear_geglu_2)
-            if last and pool_mean:          # the same residual operand down_projection would add per token
-                if trunk_f16_active():
-                    return self._pooled_down_projection(hg, w2, b2, cu, res16=s.t16 if s.t16 is not None else ops.trunk16_of(s.x),
-                                                        res16_scale=1.0 / ops.T16_SCALE)
-                if s.x is None:
-                    return self._pooled_down_projection(hg, w2, b2, cu, res16=s.x16, res16_scale=1.0 / s.scale)
-                return self._pooled_down_projection(hg, w2, b2, cu, res_f32=s.x)
-            if last:        # the encoder's last layer feeds the pooling, not a LayerNorm: plain fp32 result
-                if s.x is None or trunk_f16_active():    # 16-bit trunk: the layer input exists as its trunk copy only
-                    return down_projection(hg, w2, b2, s, keep_x=True, need_t16=False).x
-                return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=s.x)
-            # 16-bit trunk (layers.trunk16_enabled): the next layer reads the 16-bit copies + statistics only
-            return down_projection(hg, w2, b2, s, keep_x)
-        src = _as_tensor(src)
-        h = ops.layernorm(src, self.norm1.weight, self.norm1.bias)
-        x1 = self.MHA.fused(h, src, cu, max_seqlen)
-        h = ops.layernorm(x1, self.norm2.weight, self.norm2.bias)
-        w1, b1 = packed_linear(self.linear_geglu_1, geglu=True)
-        hg = ops.gemm(h, w1, b1, ops.EPI_GEGLU_BF16)
-        w2, b2 = packed_linear(self.linear_geglu_2)
+        s = layer_streams(self, src)[0]
+        # (folded, x1 is read only through norm2 -> linear_geglu_1: no fp32 store, and its residual is the 16-bit copy of the input)
+        x1 = self.MHA.self_block(s, self.norm1, cu, max_seqlen, qkv=qkv)
         if last and pool_mean:
-            return self._pooled_down_projection(hg, w2, b2, cu, res_f32=src)
-        return ops.gemm(hg, w2, b2, ops.EPI_RES_F32, residual=src)
+            return feed_forward(x1, self.norm2, self, s,
+                                pooled=lambda hg, w2, b2, **res: self._pooled_down_projection(hg, w2, b2, cu, **res))
+        # the encoder's last layer feeds the pooling, not a LayerNorm: plain fp32 rows.  Otherwise, 16-bit trunk
+        # (layers.trunk16_enabled): the next layer reads the 16-bit copies + statistics only
+        return feed_forward(x1, self.norm2, self, s, keep_x=keep_x, rows32=last)
 
     def forward(self, src, src_key_padding_mask=None, precision=torch.float32):
         """Reference signature on padded [b, L, d] input; padded rows of the result are left as the
         reference leaves them only where they matter (valid rows); pad rows are returned as zeros."""
-        from ..seq2gene.modules.layers import _as_tensor, pad_input, unpad_input, _cu_from_padded
         b, L = src.shape[:2]
         if src_key_padding_mask is None:
             out = _as_tensor(self.forward_packed(src.reshape(b * L, -1).float().contiguous(), _cu_from_padded(b, L, src.device), L))
