@@ -317,6 +317,8 @@ int vf_rowdot_softplus(const float* x, const float* w, const float* b, float* ou
                        int64_t n, int d, int softplus, void* stream);
 
 /* Max pool over the rows [cu[w], cu[w+1]) of x: out fp32 [W, d] (pool_outputs "max", model_combined_modulator.py:380-389).
+ * An empty window gives -inf; a NaN anywhere in a window's column gives NaN for that column (the reference's torch.max
+ * propagates NaN, it does not skip it).
  * Row sum with optional row indirection: out[i] = a[idx_a ? idx_a[i] : i] + b[idx_b ? idx_b[i] : i], fp32 [n, d]
  * (gene-stream residual `use_res`, model_combined_modulator.py:253-254,284-285; AddContext, layers.py:558-573). */
 int vf_segment_max(const float* x, const int32_t* cu_seqlens, float* out, int W, int d, void* stream);

@@ -216,12 +216,14 @@ def layer_norm(x, w, b):
     return F.layer_norm(x, (x.shape[-1],), w, b, 1e-5)
 
 
-def attention(q, k, v, slopes, rnd: Rounding, q_log2: bool = False):
+def attention(q, k, v, slopes, rnd: Rounding, q_log2: bool = False, q_at_start: bool = False):
     """Textbook restatement of flash-attn's varlen forward for ONE sequence [3p].
     q [sq,H,dh], k/v [sk,H,dh] (already rounded to the storage dtype by their producer).
     scores fp32, ALiBi bias -slope*|i + (sk - sq) - j|, softmax fp32; P is rounded to the
     operand dtype before PV while the normaliser is summed from the unrounded P.
-    q_log2: q already carries softmax_scale * log2(e) (Rounding.q_prescale): q . k is the base-2 logit."""
+    q_log2: q already carries softmax_scale * log2(e) (Rounding.q_prescale): q . k is the base-2 logit.
+    q_at_start: the ALiBi query positions count from the START of the key sequence, bias -slope*|i - j|
+    (VF_ATTN_Q_AT_START); the default is flash-attn's end alignment."""
     dh = q.shape[-1]
     if q_log2:
         # base-2 logits as the matrix pipe delivers them; the kernels exponentiate them directly (or, for rows outside the
@@ -230,7 +232,7 @@ def attention(q, k, v, slopes, rnd: Rounding, q_log2: bool = False):
         s2 = torch.einsum("qhd,khd->hqk", q, k)
         if slopes is not None:
             sq, sk = q.shape[0], k.shape[0]
-            i = torch.arange(sq)[:, None] + (sk - sq)
+            i = torch.arange(sq)[:, None] + (0 if q_at_start else sk - sq)
             j = torch.arange(sk)[None, :]
             s2 = s2 - (slopes.to(s2.dtype) * math.log2(math.e))[:, None, None] * (i - j).abs().to(s2.dtype)[None]
         pr = rnd.r(torch.exp2(s2 - torch.ceil(s2.max(dim=-1, keepdim=True).values)))
@@ -239,7 +241,7 @@ def attention(q, k, v, slopes, rnd: Rounding, q_log2: bool = False):
     s = torch.einsum("qhd,khd->hqk", q, k) * (1.0 / math.sqrt(dh))
     if slopes is not None:
         sq, sk = q.shape[0], k.shape[0]
-        i = torch.arange(sq)[:, None] + (sk - sq)
+        i = torch.arange(sq)[:, None] + (0 if q_at_start else sk - sq)
         j = torch.arange(sk)[None, :]
         s = s - slopes.to(s.dtype)[:, None, None] * (i - j).abs().to(s.dtype)[None]
     m = s.max(dim=-1, keepdim=True).values

@@ -5,6 +5,15 @@ import torch
 from variantformer_amd.utils.synthetic import fill_state_dict
 
 
+def _rand(shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(shape, generator=g) * 2 - 1) * scale
+
+
+def _bf(x):
+    return x.to(torch.bfloat16).to(torch.float32)
+
+
 def erel(a, b):
     """element-wise: max |a-b| / (|b| + rms(b)), so that small elements count (not the max-norm)."""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)

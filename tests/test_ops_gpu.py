@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import vf_oracle as O
+from tests.helpers import _bf, _rand
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +20,6 @@ def ops():
     from variantformer_amd import _lib
     _lib.load()      # must be the in-tree HIP library; raises if missing
     return _ops
-
-
-def _rand(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.rand(shape, generator=g) * 2 - 1) * scale
-
-
-def _bf(x):
-    return x.to(torch.bfloat16).to(torch.float32)
 
 
 def _rel_err(a, b):

@@ -542,7 +542,8 @@ __global__ __launch_bounds__(256) void affine_rows_kernel(const float* __restric
     }
 }
 
-// segment max (max pool over the tokens of a sequence): one block per window, threads over float4 columns
+// segment max (max pool over the tokens of a sequence): one block per window, threads over float4 columns.  A NaN in a
+// window's column is the result of that column, as torch.max returns it in the reference.
 __global__ __launch_bounds__(256) void segment_max_kernel(const float* __restrict__ x, const int32_t* __restrict__ cu,
                                                          float* __restrict__ out, int d) {
     const int w = blockIdx.x;
@@ -553,7 +554,7 @@ __global__ __launch_bounds__(256) void segment_max_kernel(const float* __restric
         for (int t = a; t < e; ++t) {
             const f32x4_t v = reinterpret_cast<const f32x4_t*>(x + (int64_t)t * d)[c];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = fmaxf(acc[k], v[k]);
+            for (int k = 0; k < 4; ++k) acc[k] = (acc[k] >= v[k] || acc[k] != acc[k]) ? acc[k] : v[k];   // NaN stays (fmaxf drops it)
         }
         reinterpret_cast<f32x4_t*>(out + (int64_t)w * d)[c] = acc;
     }
