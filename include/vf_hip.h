@@ -60,7 +60,10 @@ const char* vf_last_kernel(int which);
  * (layers.py:78-80,159-162; seq2reg/modules.py:145-147,184-187), cre_map/gene_map
  * (seq2gene/model_combined_modulator.py:502-507,610-612), TissueExpressionHeads Linear layers
  * (layers.py:1078-1087).  Requires K % 8 == 0, N % 8 == 0 (N % 32 == 0 for GEGLU); fast MFMA
- * path when K % 64 == 0. */
+ * path when K % 64 == 0.
+ * Non-finite operands (every vf_gemm* entry): a NaN in A makes its output row NaN, one in a W row or in bias[n] its
+ * output column, one in the residual that element -- every other element keeps the bits of the call without it; 16-bit outputs
+ * are rounded to nearest even, fp16 values beyond 65504 become +-Inf and fp16 subnormals are kept, as torch's cast does. */
 int vf_gemm_bf16(const void* A, int64_t lda, const void* W, const float* bias,
                  const float* residual, int64_t ldr, void* out, int64_t ldo,
                  int M, int N, int K, int epilogue, void* stream);
@@ -150,7 +153,10 @@ int vf_pack_geglu_rows(const void* W, const float* bias, void* W_out, float* bia
  * q=base, k=base+H*dh, v=base+2*H*dh with row stride 3*H*dh).  bf16 in/out, fp32 softmax and
  * accumulation.  dh in {32, 48, 64, 96, 128} (every multiple of 8 up to 256: vf_attn_varlen_fwd_v3).  cu_seqlens_*: int32 [n_seq+1] device arrays.
  * alibi_slopes: fp32 [H] device array or NULL.  Sequences with 0 queries are skipped; the rows of
- * queries whose key sequence is empty are written as zeros (flash-attn's convention). */
+ * queries whose key sequence is empty are written as zeros (flash-attn's convention).
+ * Non-finite operands (every vf_attn_* entry): a NaN in K makes every output of its (sequence, head) NaN, one in V
+ * its column there, one in a query row that row of the head; every other sequence, head, column and row keeps the bits of the
+ * call without it.  An Inf in V gives a non-finite column (a one-key sequence returns its V row exactly, +-Inf included). */
 int vf_attn_varlen_fwd(const void* q, const void* k, const void* v, void* out,
                        int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride,
                        const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
@@ -235,7 +241,8 @@ int vf_attn_varlen_fwd_rows(const void* q, const void* k, const void* v, void* o
  * log(count) added to the logit.  q [tokens, >= H*dh] 16-bit, pre-scaled by softmax_scale * log2 e (VF_ATTN_Q_LOG2 form);
  * kv_table [C, >= 2*H*dh] 16-bit = (K | V) of the C <= 16 distinct rows, heads packed (head, dh); log2_count fp32 [n_seq, C] =
  * log2 of how often row c occurs among sequence s's keys (-inf: not at all; every sequence holds >= 1 key);
- * out [tokens, >= H*dh] 16-bit.  fp32 scores, fp32-normalised weights, one rounding of the output. */
+ * out [tokens, >= H*dh] 16-bit.  fp32 scores, fp32-normalised weights, one rounding of the output.  A row with log2_count = -inf
+ * is not among the sequence's keys: nothing in it, a NaN included, reaches that sequence's outputs. */
 int vf_attn_counted_keys(const void* q, int64_t q_stride, const void* kv_table, int64_t kv_stride, const float* log2_count,
                          const int32_t* cu_seqlens_q, int n_seq, int max_seqlen_q, int C, int H, int dh,
                          void* out, int64_t o_stride, int operand_dtype, void* stream);

@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
 #pragma unroll
         for (int i = 0; i < NLD2; ++i) {
             int key = t * BKV + kv_row[i];
-            key = key < len_k ? key : len_k - 1;                     // finite data for masked keys
+            key = key < len_k ? key : len_k - 1;                     // K: finite data for masked keys; V: in bounds only (write_lds zeroes it)
             const unsigned off = __umul24((unsigned)key, kv_stride[i]);
             kvreg[i] = *reinterpret_cast<const u32x4_t*>(kv_src[i] + off);
         }
@@ -462,7 +462,10 @@ __global__ __launch_bounds__(256, (QL && QG == 2 && ALIBI && DH <= 48 ? 3 : 1)) 
             const int row = ci / CPR, c = ci % CPR;
             const int off = is_v ? K_TILE_BYTES + row * VROW + (c << 4)
                                  : row * K_ROW_BYTES + ((c ^ KLayout<DH>::swz(row)) << 4);
-            *reinterpret_cast<u32x4_t*>(sK + off) = (PAD && c >= dh / 8) ? (u32x4_t){0u, 0u, 0u, 0u} : kvreg[i];
+            // V rows past the sequence end are staged as zeros: their p is 0, and 0 x Inf = NaN would turn an Inf in the
+            // replicated last V row into NaN (for finite V the same bits: the products are zeros either way)
+            const bool zero = (PAD && c >= dh / 8) || (is_v && t * BKV + row >= len_k);
+            *reinterpret_cast<u32x4_t*>(sK + off) = zero ? (u32x4_t){0u, 0u, 0u, 0u} : kvreg[i];
         }
         if (HwMask<DH>::value && tid < BKV)          // pad slot d = DH of every key row: 0 or the mask value
             *reinterpret_cast<u32x4_t*>(sK + tid * K_ROW_BYTES + ((CPR ^ ((tid >> 1) & 7)) << 4)) =
@@ -634,14 +637,17 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnArgs<PAD> P) {
 #pragma unroll
         for (int i = 0; i < NLD2; ++i) {
             int key = t * BKV + kv_row[i];
-            key = key < len_k ? key : len_k - 1;                     // finite data for masked keys
+            key = key < len_k ? key : len_k - 1;                     // K: finite data for masked keys; V: in bounds only (write_lds zeroes it)
             kvreg[i] = *reinterpret_cast<const u32x4_t*>(kv_src[i] + __umul24((unsigned)key, kv_stride[i]));
         }
     };
-    auto write_lds = [&](int stage) {
+    auto write_lds = [&](int stage, int t) {
 #pragma unroll
-        for (int i = 0; i < NLD2; ++i)
-            *reinterpret_cast<u32x4_t*>(smem + stage * STAGE + kv_off[i]) = kv_pad[i] ? (u32x4_t){0u, 0u, 0u, 0u} : kvreg[i];
+        for (int i = 0; i < NLD2; ++i) {
+            // V rows past the sequence end are staged as zeros (p = 0 there, and 0 x Inf = NaN; see attn_fwd_kernel)
+            const bool zero = kv_pad[i] || (tid + 256 * i >= NCHUNK && t * BKV + kv_row[i] >= len_k);
+            *reinterpret_cast<u32x4_t*>(smem + stage * STAGE + kv_off[i]) = zero ? (u32x4_t){0u, 0u, 0u, 0u} : kvreg[i];
+        }
     };
 
     // fragment addresses inside a stage
@@ -754,12 +760,12 @@ __global__ __launch_bounds__(256) void attn_x32_kernel(AttnArgs<PAD> P) {
     const bool active = qb0 + wave * QB * 32 < len_q;                 // wave-uniform
     auto pass = [&](auto fast_c) {
         load_regs(0);
-        write_lds(0);
+        write_lds(0, 0);
         __syncthreads();
         for (int t = 0; t + 1 < nkv; ++t) {
             load_regs(t + 1);
             if (active) tile(smem + (t & 1) * STAGE, t * BKV, std::false_type{}, fast_c);
-            write_lds((t + 1) & 1);
+            write_lds((t + 1) & 1, t + 1);
             __syncthreads();
         }
         if (active) tile(smem + ((nkv - 1) & 1) * STAGE, (nkv - 1) * BKV, std::true_type{}, fast_c);
@@ -903,7 +909,7 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
         }
         q_pos[qg] = (float)(q_abs[qg] + (P.q_at_start ? 0 : len_k - len_q));
     }
-    // ---- stage K (swizzled, zero pad chunks) and V; rows >= len_k replicate the last key (finite, masked later)
+    // ---- stage K (swizzled, zero pad chunks) and V; K rows >= len_k replicate the last key (masked later), V rows are zeros
     const unsigned short* kbase = P.k + (int64_t)k_tok0 * P.k_stride + h * dh;
     const unsigned short* vbase = P.v + (int64_t)k_tok0 * P.v_stride + h * dh;
     {
@@ -917,7 +923,8 @@ __global__ __launch_bounds__(256, (QG >= 2 ? 2 : 4)) void attn_short_kernel(Attn
             if (ci < nchunks && cc < dh / 8) {
                 const int key = row < len_k ? row : len_k - 1;
                 kbuf[it] = *reinterpret_cast<const u32x4_t*>(kbase + (int64_t)key * P.k_stride + cc * 8);
-                vbuf[it] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)key * P.v_stride + cc * 8);
+                // (V rows past the sequence end stay zeros: p = 0 there, and 0 x Inf = NaN; see attn_fwd_kernel)
+                if (row < len_k) vbuf[it] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)key * P.v_stride + cc * 8);
             }
         }
 #pragma unroll
@@ -1058,7 +1065,7 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnArgs<PAD> P, in
                 qf[ps][qg][ks] = *reinterpret_cast<frag_t*>(&raw);
             }
         }
-    // ---- stage K (swizzled, zero pad chunks) and V; rows >= len_k replicate the last key (finite, masked later)
+    // ---- stage K (swizzled, zero pad chunks) and V; K rows >= len_k replicate the last key (masked later), V rows are zeros
     const unsigned short* kbase = P.k + h * dh;
     const unsigned short* vbase = P.v + h * dh;
     {
@@ -1078,7 +1085,8 @@ __global__ __launch_bounds__(256, 3) void attn_short2_kernel(AttnArgs<PAD> P, in
             vbuf[it] = (u32x4_t){0u, 0u, 0u, 0u};
             if (row < rows_v && cc < dh / 8) {
                 if (row < rows_k) kbuf[it] = *reinterpret_cast<const u32x4_t*>(kbase + src[it] * P.k_stride + cc * 8);
-                vbuf[it] = *reinterpret_cast<const u32x4_t*>(vbase + src[it] * P.v_stride + cc * 8);
+                // (V rows past the sequence end stay zeros: p = 0 there, and 0 x Inf = NaN; see attn_fwd_kernel)
+                if (row < len_k) vbuf[it] = *reinterpret_cast<const u32x4_t*>(vbase + src[it] * P.v_stride + cc * 8);
             }
         }
 #pragma unroll
@@ -1575,6 +1583,12 @@ __global__ __launch_bounds__(256) void attn_counted_keys_kernel(const unsigned s
         float sc[16];
         float m = -INFINITY;
         for (int c = 0; c < C; ++c) {
+            // a row this sequence does not hold is not among its keys: its K / V values -- a NaN included -- must not reach
+            // the result (NaN + -inf = NaN, 0 x NaN = NaN).  Block-uniform; for finite rows the same bits as weighting by 0.
+            if (sL[c] == -INFINITY) {
+                sc[c] = -INFINITY;
+                continue;
+            }
             float a = 0.f;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
@@ -1583,7 +1597,7 @@ __global__ __launch_bounds__(256) void attn_counted_keys_kernel(const unsigned s
 #pragma unroll
                 for (int e = 0; e < 8; ++e) a = __builtin_fmaf(qf[8 * j + e], f[e], a);
             }
-            a += sL[c];                                   // -inf for a label this sequence does not hold
+            a += sL[c];
             sc[c] = a;
             m = __builtin_fmaxf(m, a);
         }
@@ -1592,6 +1606,7 @@ __global__ __launch_bounds__(256) void attn_counted_keys_kernel(const unsigned s
         for (int d = 0; d < DH; ++d) o[d] = 0.f;
         float l = 0.f;
         for (int c = 0; c < C; ++c) {
+            if (sL[c] == -INFINITY) continue;
             const float pc = __builtin_amdgcn_exp2f(sc[c] - m);
             l += pc;
 #pragma unroll
@@ -1694,8 +1709,10 @@ __global__ __launch_bounds__(256) void softmax_counted_kernel(const float* __res
     unsigned short* op = out + (int64_t)(tok0 + t) * ldo + h * Cp;
 #pragma unroll
     for (int c = 0; c < 16; c += 2) {
-        if (c + 1 < Cp) *reinterpret_cast<unsigned int*>(op + c) = Op16<DT>::pack2(v[c] * inv, v[c + 1] * inv);
-        else if (c < Cp) op[c] = (unsigned short)(Op16<DT>::pack2(v[c] * inv, 0.f) & 0xffffu);
+        // the padding slots c >= C are zero whatever the row holds (0 x (1 / NaN) would make them NaN)
+        const float w0 = c < C ? v[c] * inv : 0.f, w1 = c + 1 < C ? v[c + 1] * inv : 0.f;
+        if (c + 1 < Cp) *reinterpret_cast<unsigned int*>(op + c) = Op16<DT>::pack2(w0, w1);
+        else if (c < Cp) op[c] = (unsigned short)(Op16<DT>::pack2(w0, 0.f) & 0xffffu);
     }
 }
 

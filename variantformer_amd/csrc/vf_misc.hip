@@ -109,12 +109,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 //          LayerNorm accuracy there;
 //   bit 1: a row may hold an element of magnitude >= abs_limit (|x_i - mean| <= sqrt(D * var), so |mean| + sqrt(D * var) bounds
 //          every element): its scaled fp16 copies (operand copy of an fp16 stream, the fp16 trunk copy) could overflow to inf.
+//          Raised for finite rows only (an infinite variance of finite elements included): a row that already holds a NaN
+//          or an Inf has a NaN bound and raises nothing.
 // Either bit makes the model recompute the batch with the separate-LayerNorm fp32-stream path.  Rare path: atomicOr.
 __device__ __forceinline__ void ln_alert(int* alert, float mean, float var, float rstd, int D, float ratio_limit, float abs_limit) {
     if (!alert) return;
     int bits = 0;
     if (fabsf(mean) * rstd > ratio_limit) bits |= 1;
-    if (abs_limit > 0.f && !(fabsf(mean) + sqrtf((float)D * var) < abs_limit)) bits |= 2;     // also true for inf / NaN rows
+    // (false for a row whose statistics are NaN, i.e. whose fp32 values already hold a NaN or an Inf: the separate LayerNorm
+    // cannot mend it, and recomputing the batch for it would move the bits of the healthy genes that share the batch)
+    if (abs_limit > 0.f && fabsf(mean) + sqrtf((float)D * var) >= abs_limit) bits |= 2;
     if (bits) atomicOr(alert, bits);
 }
 
