@@ -247,6 +247,35 @@ int vf_attn_counted_keys(const void* q, int64_t q_stride, const void* kv_table, 
                          const int32_t* cu_seqlens_q, int n_seq, int max_seqlen_q, int C, int H, int dh,
                          void* out, int64_t o_stride, int operand_dtype, void* stream);
 
+/* Softmax PROBABILITIES of selected query rows, in fp32 (added under ABI 13: a new symbol, no existing one changes, so the
+ * version stays 13): which keys did these rows look at.  No reference counterpart -- flash-attn [3p] keeps P in registers and
+ * has no such output (flash_attn_varlen_kvpacked_func's return_attn_probs is a dropout-debugging aid) -- exists for the
+ * gene -> cCRE attention maps (seq2gene/modules/layers.py:421-439 is the cross attention whose P this is).
+ *   selected row r, 0 <= r < R = cu_rows[n_seq], belongs to key sequence s when cu_rows[s] <= r < cu_rows[s + 1]; its query is
+ *   row q_rows[r] of q (q_rows int64, any order, may repeat; NULL = row r), its keys are rows cu_seqlens_k[s] ..
+ *   cu_seqlens_k[s + 1] of k.  q, k 16-bit (operand_dtype VF_BF16 / VF_F16), heads packed (head, dh) in the first H * dh columns;
+ *   base-2 logit s2 = q . k with VF_ATTN_Q_LOG2, else scale * log2(e) * (q . k); no ALiBi: VF_ATTN_Q_AT_START and unknown flag
+ *   bits are refused.  P[r, h, j] = exp2(s2 - m) / l with stats[(r * H + h) * 2 .. + 1] = (m, l), m = the row's largest logit,
+ *   l = sum_j exp2(s2 - m) (fp32 [R * H * 2]; an output, and the workspace between the two passes).  Scores, exponentials, sums
+ *   and P are fp32; nothing is rounded to 16 bits.
+ *   per_head == 0: out[r * ldo + j] = (1 / H) sum_h P[r, h, j], heads added in ascending order;
+ *   per_head == 1: out[(r * H + h) * ldo + j] = P[r, h, j].
+ *   Columns len_k(s) <= j < max_seqlen_k of a written row are 0, columns >= max_seqlen_k are not touched.  A sequence without
+ *   selected rows is skipped; a selected row whose key sequence is empty gets zeros and stats (0, 0).
+ * No atomics: the bits of a row depend on its own query and keys alone, not on the rest of the call, max_rows or max_seqlen_k.
+ * Non-finite operands: a NaN in a K row of (sequence, head) makes that head's probabilities of that sequence's
+ * rows NaN (and so their head mean), one in a query row that row; every other row keeps the bits of the call without it.
+ * dh in {32, 48, 64, 96, 128}; any other dh, a null pointer (q_rows alone may be NULL), n_seq < 0, max_rows < 0,
+ * ldo < max_seqlen_k, a stride < H * dh or a bad dtype is refused before anything is launched; so are q / k that are not
+ * 16-byte aligned or whose row strides are not multiples of 8 elements (the fragments are 16-byte loads, as in
+ * vf_attn_varlen_fwd), and stats / out that are not 4-byte aligned.  n_seq == 0 or max_rows == 0 (no selected rows) is VF_OK
+ * with nothing launched.  vf_last_kernel(1) names the kernel afterwards. */
+int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int64_t k_stride,
+                  const int64_t* q_rows, const int32_t* cu_rows, const int32_t* cu_seqlens_k,
+                  int n_seq, int max_rows, int max_seqlen_k, int H, int dh, float scale,
+                  int operand_dtype, int flags, int per_head,
+                  float* stats, float* out, int64_t ldo, void* stream);
+
 /* The same attention in LOW-RANK form (ABI 10): with C distinct key / value rows per head the logits are
  * LN(x) . (Wq_h^T k_c) -- vf_gemm_ln as a CONSUMER with fp32 output (epilogue VF_EPI_F32, new in ABI 10) against an
  * [H * Cp, D] matrix built once per weights -- and out_proj(sum_c w_c v_c) is w . (Wo_h v_c), a GEMM with K = H * Cp (Cp >= C,

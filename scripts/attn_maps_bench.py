@@ -1,0 +1,104 @@
+"""What the gene -> cCRE attention maps cost at the headline shape (bench.py's model and batch: 32 genes x 54 tissues,
+1024 cCREs, production depth): step time with the capture off, with the last gene layer only, with all gene layers, and the
+probabilities kernel's own time and its algorithmic bytes / time against the HBM peak (ops.KernelTimer).  One JSON line, also written to
+profiles/attn_maps_bench.json.
+
+    python scripts/attn_maps_bench.py [--steps 6] [--warmup 3] [--genes-per-step 32] [--layers N]
+
+A step is bench.py's step (forward_prepared + the expression matrix copied to the host); with a capture the maps stay on the
+device (`..._ms`) or are copied to the host as predict_step_with_attention does (`..._with_d2h_ms`)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E, on paper
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--genes-per-step", type=int, default=32)
+    ap.add_argument("--n-cre", type=int, default=1024)
+    ap.add_argument("--n-chunks", type=int, default=200)
+    ap.add_argument("--tissues", type=int, default=54)
+    ap.add_argument("--layers", type=int, default=None, help="override modulator depth (debug only)")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "attn_maps_bench.json"))
+    args = ap.parse_args()
+
+    import bench
+    from variantformer_amd import attn_maps, ops
+    from variantformer_amd.utils.synthetic import TISSUES_54, make_batch
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    model, hp, kw = bench.build_model(dev, args.layers)
+    G, tissues = args.genes_per_step, TISSUES_54[: args.tissues]
+    batch = make_batch(20251205, [args.n_cre] * G, [args.n_chunks] * G, [tissues] * G, 200)
+    n_layers = len(model.combined_modulator.gene_layers)
+
+    def timed(layers, d2h):
+        def step():
+            if layers is None:
+                model.forward_prepared(pb)[0].cpu()
+                return
+            with attn_maps.capture(layers) as cap:
+                model.forward_prepared(pb)[0].cpu()
+                if d2h:
+                    cap.maps.cpu()
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3
+
+    with torch.no_grad():
+        pb = model.prepare_batch(batch)
+        off = timed(None, False)
+        last = timed([n_layers - 1], False)
+        last_d2h = timed([n_layers - 1], True)
+        every = timed(list(range(n_layers)), False)
+        every_d2h = timed(list(range(n_layers)), True)
+        off_again = timed(None, False)
+        ops.TIMER = ops.KernelTimer()
+        with attn_maps.capture(list(range(n_layers))):
+            model.forward_prepared(pb)[0].cpu()
+        summ = ops.TIMER.summary()
+        ops.TIMER = None
+    k = summ["attn_probs"]
+    gbs = k["bytes"] / (k["total_ms"] * 1e-3) / 1e9
+    result = {
+        "shape": {"genes": G, "tissues": len(tissues), "n_cre": args.n_cre, "n_chunks": args.n_chunks, "gene_layers": n_layers},
+        "steps": args.steps, "warmup": args.warmup,
+        "capture_off_ms": round(off, 3), "capture_off_repeat_ms": round(off_again, 3),
+        "last_layer_ms": round(last, 3), "last_layer_with_d2h_ms": round(last_d2h, 3),
+        "all_layers_ms": round(every, 3), "all_layers_with_d2h_ms": round(every_d2h, 3),
+        "kernel": {"launches": k["launches"], "total_ms": round(k["total_ms"], 3),
+                   "ms_per_layer": round(k["total_ms"] / k["launches"], 4), "bytes": k["bytes"], "flops": k["flops"],
+                   "algorithmic_gb_per_s": round(gbs, 1), "algorithmic_gb_per_s_over_hbm_peak": round(gbs / HBM_PEAK_GBS, 4),
+                   "note": "both passes of vf_attn_probs per launch, bracketed by HIP events on the launch stream.  bytes = the "
+                           "ALGORITHMIC minimum (K once per pass + the selected queries + the map and the statistics written "
+                           "once), so the rate is algorithmic bytes / time, not traffic measured at the HBM: pass 1 reads K once "
+                           "per 32-row tile (twice at 54 rows) and a K slab that fits the last-level cache need not come from "
+                           "HBM in pass 2"},
+        "source_sha": bench.source_sha(),
+    }
+    line = json.dumps(result)
+    print(line)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

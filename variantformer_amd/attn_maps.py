@@ -1,0 +1,133 @@
+"""Gene -> cCRE attention maps: the sink the gene layers' cross attention writes its softmax probabilities into.
+
+Held in a context variable like runtime.Switches (no module globals; `with` blocks nest and restore; a thread starts
+without a capture), so a capture requested around one model's forward never reaches another thread's.  Off unless a
+`capture(...)` block is open: the layer stack then makes not one launch or allocation more than without this module.
+
+    with attn_maps.capture(layers=(0, 24), per_head=False) as cap:
+        model.forward_prepared(pb)            # or predict_launch / predict_finish
+    cap.maps                                  # fp32 [len(layers), sum T (* H), max_cre], row r = row r of `emb`
+
+Who calls what: the model's forward `begin`s the capture with the batch's selected rows (the registry-token rows, the
+only rows the expression head reads); modulator_forward_packed wraps every GENE layer in `cap.layer(i, ...)`; MHA.attend's
+cross branch asks `running()` and, inside a requested gene layer only, hands q and K to `record`.  The CRE layers run
+outside any `layer(...)` block and are never captured.  DESIGN.md section 5b.
+"""
+from __future__ import annotations
+
+import contextvars
+
+import torch
+
+from . import ops
+
+_CAP: contextvars.ContextVar = contextvars.ContextVar("vf_attn_capture", default=None)
+
+
+class Capture:
+    def __init__(self, layers, per_head: bool = False):
+        self.layers = tuple(int(i) for i in layers)     # distinct gene-layer indices, in the order of the first axis of `maps`
+        if not self.layers or len(set(self.layers)) != len(self.layers):
+            raise ValueError(f"attention maps: a capture needs distinct gene layers, got {list(self.layers)}")
+        self.per_head = bool(per_head)
+        self.maps = None          # fp32 [len(layers), R or R * H, max_k] of the most recent forward
+        self.n_rows = 0
+        self._rows = None         # (q_rows int64 [R], cu_rows int32 [n_seq + 1], max_rows, cu_k int32 [n_seq + 1], max_k)
+        self._running = None      # (slot in `layers`, compact: the query buffer holds exactly the selected rows)
+
+    def begin(self, q_rows, cu_rows, max_rows: int, cu_k, max_k: int) -> None:
+        """A forward starts: its selected rows (row q_rows[r] of the gene layers' query buffer, grouped per key sequence by
+        cu_rows) and keys.  The buffers are the forward's own: a second forward under the same capture (the LayerNorm-fold
+        recomputation) starts afresh and `maps` is then its result."""
+        self._rows = (q_rows, cu_rows, int(max_rows), cu_k, int(max_k))
+        self.n_rows = int(q_rows.numel())
+        self.maps = None
+
+    def layer(self, i: int, compact: bool = False):
+        """with cap.layer(i): gene layer i is running.  compact: its cross attention's query buffer already is the selected rows,
+        in order (the last layer's registry-rows form)."""
+        return _Layer(self, i, compact)
+
+    def record(self, q, k, n_heads: int, head_dim: int, family: str = "") -> None:
+        slot, compact = self._running
+        q_rows, cu_rows, max_rows, cu_k, max_k = self._rows
+        n_out = self.n_rows * (n_heads if self.per_head else 1)
+        if self.maps is None:
+            self.maps = torch.empty((len(self.layers), n_out, max_k), dtype=torch.float32, device=q.device)
+        if compact:
+            assert q.shape[0] == self.n_rows
+        ops.attn_probs(q, k, cu_rows, cu_k, max_rows, max_k, n_heads, head_dim, q_rows=None if compact else q_rows,
+                       q_log2=True, per_head=self.per_head, out=self.maps[slot], family=family + "_maps")
+
+
+class _Layer:
+    def __init__(self, cap: Capture, i: int, compact: bool):
+        self.cap, self.i, self.compact = cap, i, compact
+
+    def __enter__(self):
+        self.prev = self.cap._running
+        self.cap._running = (self.cap.layers.index(self.i), self.compact) if self.i in self.cap.layers else None
+        return self
+
+    def __exit__(self, *exc):
+        self.cap._running = self.prev
+        return False
+
+
+class _NoLayer:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
+_NO_LAYER = _NoLayer()
+
+
+def select_layers(n_layers: int, layers=None) -> list:
+    """The gene-layer indices a request names: None = all, negative indices count from the end; ValueError when an index is out
+    of range, when none is given, or when two name the same layer (every slot of the result is one layer's map, written once).
+    (One statement of the convention, for the model API and for the tests' oracle-side reference.)"""
+    sel = list(range(n_layers)) if layers is None else [int(i) for i in layers]
+    if not sel:
+        raise ValueError("attention maps: `layers` names no gene layer (None means all)")
+    for k, i in enumerate(sel):
+        if not -n_layers <= i < n_layers:
+            raise ValueError(f"gene layer {i} out of range (the model has {n_layers} gene layers)")
+        sel[k] = i % n_layers
+    if len(set(sel)) != len(sel):
+        raise ValueError(f"attention maps: `layers` names a gene layer twice ({sel})")
+    return sel
+
+
+def active() -> Capture | None:
+    """The capture open in this context, or None."""
+    return _CAP.get()
+
+
+def gene_layer(i: int, compact: bool = False):
+    """with attn_maps.gene_layer(i): ...  -- tells the open capture (if any) which gene layer runs inside the block."""
+    cap = _CAP.get()
+    return _NO_LAYER if cap is None else cap.layer(i, compact)
+
+
+def running() -> Capture | None:
+    """The open capture when a gene layer it asked for is running and its forward has named the selected rows; else None."""
+    cap = _CAP.get()
+    return cap if cap is not None and cap._running is not None and cap._rows is not None else None
+
+
+class capture:
+    """with attn_maps.capture(layers, per_head) as cap: every forward inside records the requested gene layers' maps."""
+
+    def __init__(self, layers, per_head: bool = False):
+        self.cap = Capture(layers, per_head)
+
+    def __enter__(self) -> Capture:
+        self.token = _CAP.set(self.cap)
+        return self.cap
+
+    def __exit__(self, *exc):
+        _CAP.reset(self.token)
+        return False

@@ -19,6 +19,12 @@ LIB = os.path.join(HERE, "libvf_hip.so")
 ARCH = "gfx950"
 # vf_attn: scores are never NaN by construction (finite inputs, -inf only as a mask), so fmaxf needs no
 # canonicalising v_max in front of every max (68 extra VALU instructions per key tile otherwise).
+# The NaN CONTRACTS of this file's kernels (vf_attn_probs: a NaN in a K row / query row makes that head's / that
+# row's probabilities NaN) therefore rest on what this compiler emits, not on what the flag guarantees: no kernel here tests for
+# NaN, a NaN operand travels through the MFMAs, v_exp, the sums and the final multiply in hardware, and v_max_f32 returns its
+# non-NaN operand.  Formally the flag lets a compiler assume the NaN away; tests/test_nonfinite_gpu.py and
+# tests/test_attn_probs_gpu.py hold every entry to the contract on the built library, so a compiler that uses the licence fails
+# them instead of shipping.
 EXTRA_FLAGS = {"vf_attn.hip": ["-fno-honor-nans"]}
 # No packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) in any device code.  Measured on MI355X in
 # round 6 (scripts/probes/pk_hazard_probe.hip, profiles/r06_d_pk_hazard_probe.log): a packed-fp32 instruction whose op_sel

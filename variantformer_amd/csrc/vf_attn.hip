@@ -1752,3 +1752,252 @@ extern "C" int vf_attn_varlen_fwd_rows(const void* q, const void* k, const void*
     return attn_dispatch<VF_F16>(q, k, v, out, q_stride, k_stride, v_stride, o_stride, cu_seqlens_q, cu_seqlens_k, n_seq,
                                  max_seqlen_q, max_seqlen_k, H, dh, alibi_slopes, scale, flags, stream, q_rows, kv_rows);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// vf_attn_probs: the softmax PROBABILITIES of a few selected query rows against their sequence's keys, in fp32 -- the quantity
+// the flash-style kernels above keep in registers, round to 16 bits for P . V and never write.  No V, no positional bias.
+// Same MFMA formulation as attn_x32_kernel (v_mfma_f32_32x32x16, S^T[key 32][query 32] = K . Q^T, A = 32 key rows, B = Q^T;
+// lane (query = lane & 31, hf = lane >> 5) ends up with keys (i & 3) + 8 (i >> 2) + 4 hf of ITS query in register i), but the
+// fragments come straight from global memory: a few dozen rows against 10^3 keys is T * N * D MACs per sequence, two waves at
+// most share a fragment (L1 serves the second), and without LDS there is no barrier an early exit could miss.
+// Two passes, `stats` = (m, l) per (row, head) between them:
+//   1. attn_probs_stats_kernel, wave = (sequence, 32-row tile, head): walks the keys in tiles of 32 with a running maximum m
+//      (the TRUE maximum of the base-2 logits, so every exponent is <= 0 whatever the magnitude) and l = sum_j exp2(s2 - m);
+//      each half wave sums its 16 keys of every tile in register order, the halves meet once at the end.
+//   2. attn_probs_kernel, block = (sequence, 64-key tile, 64-row tile), wave = one 32 x 32 quadrant: loops over the heads in
+//      ascending order, recomputes the logits with the same instructions on the same fragments as pass 1 (same bits),
+//      P = exp2(s2 - m) / l, and either stores P per head or keeps the head sum in 16 registers and stores sum / H.
+// The arithmetic of a row touches its own query, its own keys and nothing else: tile positions depend only on the row's index
+// inside its sequence and on the key index, the MFMA columns (queries) and rows (keys) are independent, and no atomics: the
+// bits depend neither on the rest of the call nor on max_rows / max_seqlen_k.  A NaN in a key row reaches l (and so every
+// probability) of that (sequence, head) alone, one in a query row that row alone; masked columns are selected to 0 / -inf, never
+// multiplied.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct ProbsParams {
+    const unsigned short* q;
+    const unsigned short* k;
+    int64_t q_stride, k_stride;
+    const int64_t* q_rows;      // selected row r's query is row q_rows[r] of q; null: row r
+    const int32_t* cu_rows;     // selected rows of sequence s: [cu_rows[s], cu_rows[s + 1])
+    const int32_t* cu_k;
+    float c;                    // base-2 logit = c * (q . k): 1 (VF_ATTN_Q_LOG2) or scale * log2(e)
+    int H, n_seq;
+    int nrt;                    // 32-row tiles per sequence (pass 1)
+    int max_k;
+    int per_head;
+    float* stats;
+    float* out;
+    int64_t ldo;
+};
+
+template <int DT, int KS>
+__device__ __forceinline__ void probs_load_frags(typename Op16<DT>::frag (&f)[KS], const unsigned short* p) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const u32x4_t raw = *reinterpret_cast<const u32x4_t*>(p + 16 * ks);
+        f[ks] = __builtin_bit_cast(typename Op16<DT>::frag, raw);
+    }
+}
+
+// base-2 logits of one 32-key x 32-query tile; keys at or past `klim` (relative to the tile's first key) are -inf
+template <int DT, int KS>
+__device__ __forceinline__ void probs_logits(const typename Op16<DT>::frag (&kf)[KS], const typename Op16<DT>::frag (&qf)[KS],
+                                             float c, int klim, int hf, float (&s)[16]) {
+    f32x16_t acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) acc = Op16<DT>::mfma32(kf[ks], qf[ks], acc);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s[i] = ((i & 3) + 8 * (i >> 2) + 4 * hf) < klim ? acc[i] * c : -INFINITY;
+}
+
+template <int DT, int DH>
+__global__ __launch_bounds__(256) void attn_probs_stats_kernel(ProbsParams P) {
+    using frag_t = typename Op16<DT>::frag;
+    constexpr int KS = DH / 16;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = lane & 31, hf = lane >> 5;
+    const long w = (long)blockIdx.x * 4 + wave;                 // (sequence, row tile, head), head fastest; wave-uniform
+    if (w >= (long)P.n_seq * P.nrt * P.H) return;
+    const int h = (int)(w % P.H), rt = (int)((w / P.H) % P.nrt), seq = (int)(w / ((long)P.H * P.nrt));
+    const int r0 = P.cu_rows[seq], n_rows = P.cu_rows[seq + 1] - r0;
+    if (rt * 32 >= n_rows) return;
+    const int k0 = P.cu_k[seq], len_k = P.cu_k[seq + 1] - k0;
+    const bool row_ok = rt * 32 + x < n_rows;                   // the other lanes repeat the sequence's last row and store nothing
+    const int r = r0 + (row_ok ? rt * 32 + x : n_rows - 1);
+    float* sp = P.stats + ((int64_t)r * P.H + h) * 2;
+    if (len_k <= 0) {                                           // no keys: stats (0, 0), the row itself is zeroed by pass 2
+        if (row_ok && hf == 0) { sp[0] = 0.f; sp[1] = 0.f; }
+        return;
+    }
+    const int64_t q_row = P.q_rows ? P.q_rows[r] : (int64_t)r;
+    frag_t qf[KS];
+    probs_load_frags<DT, KS>(qf, P.q + q_row * P.q_stride + h * DH + 8 * hf);
+    const unsigned short* kp = P.k + (int64_t)k0 * P.k_stride + h * DH + 8 * hf;
+    float m = -INFINITY, l = 0.f;
+    for (int kb = 0; kb < len_k; kb += 32) {
+        const int key = kb + x < len_k ? kb + x : len_k - 1;    // in bounds; the logit is masked below
+        frag_t kf[KS];
+        probs_load_frags<DT, KS>(kf, kp + (int64_t)key * P.k_stride);
+        float s[16];
+        probs_logits<DT, KS>(kf, qf, P.c, len_k - kb, hf, s);
+        float mx = s[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) mx = max2f(mx, s[i]);
+        mx = max2f(mx, __shfl_xor(mx, 32));
+        const float m_new = max2f(m, mx);                       // finite from the first tile on: it holds a valid key
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sum += __builtin_amdgcn_exp2f(s[i] - m_new);
+        l = l * __builtin_amdgcn_exp2f(m - m_new) + sum;
+        m = m_new;
+    }
+    l += __shfl_xor(l, 32);
+    if (row_ok && hf == 0) { sp[0] = m; sp[1] = l; }
+}
+
+// four consecutive columns of one output row: one 16-byte store where the row allows it (ldo is the caller's: rows are only
+// 4-byte aligned in general), never past column max_k
+__device__ __forceinline__ void probs_store4(float* op, int col, int max_k, f32x4_t v) {
+    if (col + 3 < max_k && (reinterpret_cast<uintptr_t>(op) & 15) == 0) {
+        *reinterpret_cast<f32x4_t*>(op) = v;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (col + e < max_k) op[e] = v[e];
+    }
+}
+
+template <int DT, int DH>
+__global__ __launch_bounds__(256) void attn_probs_kernel(ProbsParams P) {
+    using frag_t = typename Op16<DT>::frag;
+    constexpr int KS = DH / 16;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = lane & 31, hf = lane >> 5;
+    const int seq = blockIdx.z;
+    const int r0 = P.cu_rows[seq], n_rows = P.cu_rows[seq + 1] - r0;
+    const int rbase = blockIdx.y * 64 + 32 * (wave >> 1);       // this wave's quadrant: 32 rows x 32 keys; wave-uniform exits
+    if (rbase >= n_rows) return;
+    const int k0 = P.cu_k[seq], len_k = P.cu_k[seq + 1] - k0;
+    const int kbase = blockIdx.x * 64 + 32 * (wave & 1);
+    if (kbase >= P.max_k) return;
+    const bool row_ok = rbase + x < n_rows;
+    const int r = r0 + (row_ok ? rbase + x : n_rows - 1);
+    const int H = P.H;
+    const int klim = len_k - kbase;                              // keys of this tile below klim exist
+
+    if (klim <= 0) {                                             // the whole quadrant lies past the sequence's keys: zeros
+        if (row_ok) {
+            const int64_t n_out = P.per_head ? H : 1;
+            for (int64_t o = 0; o < n_out; ++o) {
+                float* op = P.out + ((int64_t)r * n_out + o) * P.ldo + kbase + 4 * hf;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) probs_store4(op + 8 * g, kbase + 4 * hf + 8 * g, P.max_k, (f32x4_t){0.f, 0.f, 0.f, 0.f});
+            }
+        }
+        return;
+    }
+
+    const int key = x < klim ? kbase + x : len_k - 1;
+    const unsigned short* kp = P.k + (int64_t)(k0 + key) * P.k_stride + 8 * hf;
+    const int64_t q_row = P.q_rows ? P.q_rows[r] : (int64_t)r;
+    const unsigned short* qp = P.q + q_row * P.q_stride + 8 * hf;
+    const float* sp = P.stats + (int64_t)r * H * 2;
+
+    float acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    // the next head's fragments and statistics are requested before this head's arithmetic
+    frag_t kf[KS], qf[KS];
+    probs_load_frags<DT, KS>(kf, kp);
+    probs_load_frags<DT, KS>(qf, qp);
+    float m = sp[0], l = sp[1];
+    for (int h = 0; h < H; ++h) {
+        const int hn = h + 1 < H ? h + 1 : h;
+        frag_t kn[KS], qn[KS];
+        probs_load_frags<DT, KS>(kn, kp + hn * DH);
+        probs_load_frags<DT, KS>(qn, qp + hn * DH);
+        const float m_n = sp[2 * hn], l_n = sp[2 * hn + 1];
+
+        float s[16];
+        probs_logits<DT, KS>(kf, qf, P.c, klim, hf, s);
+        const float inv = 1.0f / l;
+        float p[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i)                             // masked columns are 0 whatever m and l hold
+            p[i] = ((i & 3) + 8 * (i >> 2) + 4 * hf) < klim ? __builtin_amdgcn_exp2f(s[i] - m) * inv : 0.f;
+        if (P.per_head) {
+            if (row_ok) {
+                float* op = P.out + ((int64_t)r * H + h) * P.ldo + kbase + 4 * hf;
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    probs_store4(op + 8 * g, kbase + 4 * hf + 8 * g, P.max_k, (f32x4_t){p[4 * g], p[4 * g + 1], p[4 * g + 2], p[4 * g + 3]});
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] += p[i];
+        }
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) { kf[ks] = kn[ks]; qf[ks] = qn[ks]; }
+        m = m_n; l = l_n;
+    }
+    if (!P.per_head && row_ok) {
+        const float inv_h = 1.0f / (float)H;
+        float* op = P.out + (int64_t)r * P.ldo + kbase + 4 * hf;
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            probs_store4(op + 8 * g, kbase + 4 * hf + 8 * g, P.max_k,
+                         (f32x4_t){acc[4 * g] * inv_h, acc[4 * g + 1] * inv_h, acc[4 * g + 2] * inv_h, acc[4 * g + 3] * inv_h});
+    }
+}
+
+template <int DT, int DH>
+static int launch_attn_probs(const ProbsParams& P, int max_rows, hipStream_t st) {
+    const long waves = (long)P.n_seq * P.nrt * P.H;
+    hipLaunchKernelGGL((attn_probs_stats_kernel<DT, DH>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, P);
+    VF_CHECK_LAUNCH("vf_attn_probs");
+    if (P.max_k > 0) {
+        hipLaunchKernelGGL((attn_probs_kernel<DT, DH>), dim3((P.max_k + 63) / 64, (max_rows + 63) / 64, P.n_seq), dim3(256), 0, st, P);
+        VF_CHECK_LAUNCH("vf_attn_probs");
+    }
+    return VF_OK;
+}
+
+}  // namespace
+
+extern "C" int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int64_t k_stride, const int64_t* q_rows,
+                             const int32_t* cu_rows, const int32_t* cu_seqlens_k, int n_seq, int max_rows, int max_seqlen_k, int H,
+                             int dh, float scale, int operand_dtype, int flags, int per_head, float* stats, float* out, int64_t ldo,
+                             void* stream) {
+    VF_REQUIRE(q && k && cu_rows && cu_seqlens_k && stats && out, "vf_attn_probs: null pointer");
+    VF_REQUIRE(operand_dtype == VF_BF16 || operand_dtype == VF_F16, "vf_attn_probs: operand_dtype must be VF_BF16 or VF_F16");
+    VF_REQUIRE((flags & ~VF_ATTN_Q_LOG2) == 0, "vf_attn_probs: flags 0x%x: only VF_ATTN_Q_LOG2 applies (no positional bias)", flags);
+    VF_REQUIRE(legacy_dh(dh), "vf_attn_probs: head_dim %d not supported (32/48/64/96/128)", dh);
+    VF_REQUIRE(H > 0 && H <= 65535 && n_seq >= 0 && max_rows >= 0 && max_seqlen_k >= 0,
+               "vf_attn_probs: H=%d n_seq=%d max_rows=%d max_seqlen_k=%d out of range", H, n_seq, max_rows, max_seqlen_k);
+    VF_REQUIRE(ldo >= max_seqlen_k, "vf_attn_probs: ldo=%ld is below max_seqlen_k=%d", (long)ldo, max_seqlen_k);
+    VF_REQUIRE(q_stride >= (int64_t)H * dh && k_stride >= (int64_t)H * dh, "vf_attn_probs: row strides must hold H * dh = %d elements", H * dh);
+    VF_REQUIRE(q_stride % 8 == 0 && k_stride % 8 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) &&
+                   ((uintptr_t)stats % 4 == 0) && ((uintptr_t)out % 4 == 0),
+               "vf_attn_probs: q / k rows must keep 16-byte alignment");
+    if (n_seq == 0 || max_rows == 0) return VF_OK;
+    const int nrt = (max_rows + 31) / 32;
+    VF_REQUIRE(n_seq <= 65535 && (max_rows + 63) / 64 <= 65535 && ((long)n_seq * nrt * H + 3) / 4 < (1L << 31),
+               "vf_attn_probs: n_seq=%d max_rows=%d exceed the grid limit", n_seq, max_rows);
+    ProbsParams P;
+    P.q = (const unsigned short*)q; P.k = (const unsigned short*)k; P.q_stride = q_stride; P.k_stride = k_stride;
+    P.q_rows = q_rows; P.cu_rows = cu_rows; P.cu_k = cu_seqlens_k;
+    P.c = (flags & VF_ATTN_Q_LOG2) ? 1.0f : scale * 1.4426950408889634f;
+    P.H = H; P.n_seq = n_seq; P.nrt = nrt; P.max_k = max_seqlen_k; P.per_head = per_head ? 1 : 0;
+    P.stats = stats; P.out = out; P.ldo = ldo;
+    hipStream_t st = (hipStream_t)stream;
+    vf_note_kernel(1, "attn_probs_kernel");
+#define VF_PR(DT_) (dh == 32 ? launch_attn_probs<DT_, 32>(P, max_rows, st) : dh == 48 ? launch_attn_probs<DT_, 48>(P, max_rows, st) : \
+                    dh == 64 ? launch_attn_probs<DT_, 64>(P, max_rows, st) : dh == 96 ? launch_attn_probs<DT_, 96>(P, max_rows, st) : \
+                    launch_attn_probs<DT_, 128>(P, max_rows, st))
+    return operand_dtype == VF_BF16 ? VF_PR(VF_BF16) : VF_PR(VF_F16);
+#undef VF_PR
+}

@@ -164,9 +164,7 @@ class VCFDataset(Dataset):
         fast = self._get_cres_batched(table, gene_info, vcf_path)
         if fast is not None:
             return fast
-        bed = table[["chromosome", "start_cre", "end_cre", "cre_name"]].rename(
-            columns={"chromosome": "chrom", "start_cre": "start", "end_cre": "end", "cre_name": "cCRE"})
-        cres = self._extractor(self.cre_neighbour_hood).process_subject(vcf_file=vcf_path, bed_regions=bed)
+        cres = self._per_window_cres(table, vcf_path)
         minus = gene_info["strand"] != "+"
         if gene_info["strand"] == "-":
             cres = cres.iloc[::-1]
@@ -182,6 +180,61 @@ class VCFDataset(Dataset):
         labels = np.full(n, self.cre_to_idx["Low-DNase"], dtype=np.int64)
         return torch.from_numpy(X), torch.from_numpy(masks), torch.from_numpy(ref_labels), torch.from_numpy(labels)
 
+    def _per_window_cres(self, table: pd.DataFrame, vcf_path: str) -> pd.DataFrame:
+        """The per-window path's frame (one consensus per window; process_subject drops windows without a sequence and orders
+        the rest), plus-strand order; its attrs["bed_rows"] are the manifest rows it kept, in that order."""
+        bed = table[["chromosome", "start_cre", "end_cre", "cre_name"]].rename(
+            columns={"chromosome": "chrom", "start_cre": "start", "end_cre": "end", "cre_name": "cCRE"})
+        return self._extractor(self.cre_neighbour_hood).process_subject(vcf_file=vcf_path, bed_regions=bed)
+
+    def _batched_windows(self, table: pd.DataFrame):
+        """(chrom, manifest rows, starts, ends) of the windows when the batched builder serves this manifest -- all windows on
+        one chromosome the genome holds, a span that fits in memory -- else None (the per-window path takes over).  Plus-strand
+        order: sorted stably by start (process_subject sorts by start), windows that come out empty dropped (they yield no row
+        there either); starts / ends are the padded, clipped bounds.  ONE statement of which path builds a gene's windows and
+        in what order, for _get_cres_batched and cre_table."""
+        from ..utils.data_process import open_fasta
+        chroms = table["chromosome"].to_numpy()
+        if len(chroms) == 0 or (chroms != chroms[0]).any():
+            return None
+        chrom = str(chroms[0])
+        fa = open_fasta(self.fasta_path)
+        if chrom not in fa.index:
+            return None
+        nh = self.cre_neighbour_hood
+        start, end = table["start_cre"].to_numpy(), table["end_cre"].to_numpy()
+        order = np.argsort(start, kind="stable")
+        starts = np.maximum(0, start[order].astype(np.int64) - nh)
+        ends = np.minimum(end[order].astype(np.int64) + nh, fa.length(chrom))
+        keep = ends > starts
+        rows, starts, ends = order[keep], np.ascontiguousarray(starts[keep]), np.ascontiguousarray(ends[keep])
+        if len(starts) == 0 or int(ends.max() - starts.min()) > 64_000_000:
+            return None
+        return chrom, rows, starts, ends
+
+    def cre_table(self, gene_id: str, vcf_path: str = None) -> pd.DataFrame:
+        """The manifest rows (chromosome, start_cre, end_cre, cre_name) of a gene's cCRE windows in exactly the row order of its
+        `cre_sequences` (_get_cres): what names the columns of an attention map (VCFProcessor.predict_with_attention).  The order
+        comes from the code that builds the sample: the batched builder's plan (_batched_windows: sorted stably by start, empty
+        windows dropped) where it serves the manifest, else the per-window path itself (process_subject's kept rows; it builds
+        the windows' consensus to learn which ones yield a sequence, so it takes the gene's VCF: `vcf_path`, default the
+        query's); reversed for a minus-strand gene."""
+        cols = ["chromosome", "start_cre", "end_cre", "cre_name"]
+        table = pd.read_csv(self.gene_cre_manifest.get_file_path(gene_id), usecols=cols)[cols]
+        plan = self._batched_windows(table)
+        if plan is not None:
+            rows = plan[1]
+        else:
+            if vcf_path is None:
+                vcf_path = self.vcf_path
+                if "vcf_path" in self.query_df.columns:
+                    hit = self.query_df.loc[self.query_df["gene_id"] == gene_id, "vcf_path"]
+                    vcf_path = hit.iloc[0] if len(hit) else vcf_path
+            rows = self._per_window_cres(table, vcf_path).attrs["bed_rows"]
+        if self._get_gene_info(gene_id)["strand"] == "-":
+            rows = rows[::-1]
+        return table.iloc[rows].reset_index(drop=True)
+
     def _get_cres_batched(self, table: pd.DataFrame, gene_info: dict, vcf_path: str):
         """Same result as the per-window path above from ONE native call (vf_build_windows: consensus -> reverse
         complement -> BPE -> pad, for all windows of the gene; ~5x less host time per gene).  Returns None when the
@@ -192,23 +245,12 @@ class VCFDataset(Dataset):
         from .. import _lib
         from ..utils.data_process import ConsensusError, _INDEL_POLICIES, open_fasta, open_vcf
         # (the manifest's own columns as arrays: building the renamed 4-column frame first cost 2 ms of pandas per gene)
-        chroms = table["chromosome"].to_numpy()
-        if len(chroms) == 0 or (chroms != chroms[0]).any():
+        plan = self._batched_windows(table)
+        if plan is None:
             return None
-        chrom = str(chroms[0])
-        bed = {"start": table["start_cre"].to_numpy(), "end": table["end_cre"].to_numpy(), "cCRE": table["cre_name"].to_numpy()}
+        chrom, rows, starts, ends = plan
+        names = table["cre_name"].to_numpy()[rows]
         fa = open_fasta(self.fasta_path)
-        if chrom not in fa.index:
-            return None
-        nh = self.cre_neighbour_hood
-        order = np.argsort(bed["start"], kind="stable")          # process_subject sorts by start
-        starts = np.maximum(0, bed["start"][order].astype(np.int64) - nh)
-        ends = np.minimum(bed["end"][order].astype(np.int64) + nh, fa.length(chrom))
-        names = bed["cCRE"][order]
-        keep = ends > starts                                                 # empty windows yield no row there either
-        starts, ends, names = np.ascontiguousarray(starts[keep]), np.ascontiguousarray(ends[keep]), names[keep]
-        if len(starts) == 0 or int(ends.max() - starts.min()) > 64_000_000:
-            return None
         span0 = int(starts.min())
         ref = fa.fetch(chrom, span0, int(ends.max())).encode("ascii")
         if self.bpe._h is None:

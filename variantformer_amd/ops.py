@@ -532,6 +532,50 @@ def attn_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_q: torch.T
     return out
 
 
+def attn_probs(q: torch.Tensor, k: torch.Tensor, cu_rows: torch.Tensor, cu_k: torch.Tensor, max_rows: int, max_k: int,
+               n_heads: int, head_dim: int, q_rows: torch.Tensor | None = None, q_log2: bool = True, per_head: bool = False,
+               scale: float | None = None, out: torch.Tensor | None = None, family: str = ""):
+    """fp32 softmax probabilities of selected query rows against their sequence's keys (vf_attn_probs; attention maps).
+    q [*, >=H*dh] / k [tk, >=H*dh] 16-bit row-strided views; selected row r (cu_rows int32 [n_seq + 1] groups them per key
+    sequence) is row q_rows[r] of q (int64; None: row r, and q holds exactly the selected rows).  Returns (out, stats):
+    out fp32 [R, max_k] = the head mean, or [R * H, max_k] per head (columns past a sequence's keys are 0; a caller's `out`
+    may be wider: columns >= max_k are left alone); stats fp32 [R, H, 2] = (m, l) of every row and head, base 2."""
+    _dev(q, k, cu_rows, cu_k, q_rows, out)
+    for t in (q, k):
+        assert _is16(t.dtype) and t.dtype == q.dtype and t.dim() == 2 and t.stride(1) == 1
+    assert cu_rows.dtype == torch.int32 and cu_k.dtype == torch.int32 and cu_rows.numel() == cu_k.numel()
+    D = n_heads * head_dim
+    if q_rows is not None:
+        assert q_rows.dtype == torch.int64 and q_rows.is_contiguous()
+    R = q.shape[0] if q_rows is None else q_rows.numel()
+    n_out = R * n_heads if per_head else R
+    if out is None:
+        out = torch.empty((n_out, int(max_k)), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == n_out and out.shape[1] >= max_k and out.stride(1) == 1
+    stats = torch.empty((R, n_heads, 2), dtype=torch.float32, device=q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(head_dim)
+    tk = k.shape[0]
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_attn_probs(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), _ptr(q_rows), cu_rows.data_ptr(),
+                                        cu_k.data_ptr(), cu_rows.numel() - 1, int(max_rows), int(max_k), n_heads, head_dim,
+                                        float(scale), _dt(q.dtype), ATTN_Q_LOG2 if q_log2 else 0, int(bool(per_head)),
+                                        stats.data_ptr(), out.data_ptr(), out.stride(0), _stream()), "vf_attn_probs")
+
+    def flops():       # 2 passes x 2 * sum_seq(rows * len_k) * H * dh, evaluated after the timed replay
+        lr = (cu_rows[1:] - cu_rows[:-1]).double()
+        lk = (cu_k[1:] - cu_k[:-1]).double()
+        return 4.0 * float((lr * lk).sum().item()) * D
+    # K is read once per pass; the selected queries twice; out and stats written once
+    _run(launch, lambda: ("attn_probs", flops, 2.0 * D * (2 * tk + 2 * R) + 4.0 * n_out * int(max_k) + 16.0 * R * n_heads,
+                          f"H={n_heads} dh={head_dim} max_rows={int(max_rows)} max_k={int(max_k)}" + (" per_head" if per_head else ""),
+                          family or _SCOPE))
+    return out, stats
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

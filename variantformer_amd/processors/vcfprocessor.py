@@ -136,6 +136,37 @@ class VCFProcessor:
         predictions = trainer.predict(model, dataloader, ckpt_path=checkpoint_path)
         return self.format_output(vcf_dataset.query_df, predictions)
 
+    def predict_with_attention(self, model, checkpoint_path, trainer, dataloader, vcf_dataset, layers=None, per_head=False):
+        """`predict`'s frame plus the gene -> cCRE attention maps of the same forwards (no reference counterpart: flash-attn
+        returns no probabilities).  New columns, one entry per gene:
+          cre_attention         fp32 [len(layers), tissues, cCREs] (per_head: [len(layers), tissues, heads, cCREs]) -- how much the
+                                registry token of each requested tissue attends to each of the gene's cCRE windows in gene
+                                layer layers[k]; tissues in the order of the query, cCREs in the order of cre_names;
+          cre_attention_layers  the gene-layer indices (layers=None: all; negative: from the end);
+          cre_names, cre_start, cre_end   the manifest rows of the windows, where the dataset can name them (cre_table).
+        A plain loop over the loader (the maps are read back per batch)."""
+        model.trainer = trainer
+        model.eval()
+        predictions = [model.predict_step_with_attention(batch, i, layers=layers, per_head=per_head)
+                       for i, batch in enumerate(dataloader)]
+        try:       # as Trainer.predict: what the self-healing LayerNorm fold did during this pass
+            from ..seq2gene.model_combined_modulator import ln_fold_state
+            trainer.ln_fold_state = ln_fold_state(model)
+        except Exception:                                     # a model class without the fold
+            trainer.ln_fold_state = None
+        df = self.format_output(vcf_dataset.query_df, predictions)
+        maps = [m for p in predictions for m in p["cre_attention"]]
+        df["cre_attention"] = pd.Series(maps, index=df.index, dtype=object)
+        df["cre_attention_layers"] = pd.Series([list(p["cre_attention_layers"]) for p in predictions for _ in p["cre_attention"]],
+                                               index=df.index, dtype=object)
+        if hasattr(vcf_dataset, "cre_table"):
+            tables = [vcf_dataset.cre_table(g) for g in df["gene_id"]]
+            for g, t, m in zip(df["gene_id"], tables, maps):         # a name per map column, or no names at all
+                assert len(t) == m.shape[-1], f"{g}: cre_table names {len(t)} windows, the map has {m.shape[-1]} columns"
+            for col, src in (("cre_names", "cre_name"), ("cre_start", "start_cre"), ("cre_end", "end_cre")):
+                df[col] = pd.Series([t[src].tolist() for t in tables], index=df.index, dtype=object)
+        return df
+
     def predict_distributed(self, model, checkpoint_path, trainer, vcf_dataset, batch_size: int | None = None, costs=None,
                             **loader_kwargs):
         """Multi-GPU vcf2exp (the reference is single-device, vcfprocessor.py:252-258): call from every rank

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib, ops, runtime, weights
+from .. import _lib, attn_maps, ops, runtime, weights
 from ..utils.constants import REF_CREs
 from ..utils.functions import precision2dtype
 from .modules.layers import (AddContext, ContextFlashAttentionEncoderLayer, ContextFlashCrossAttentionEncoderLayer,
@@ -297,8 +297,9 @@ def modulator_forward_packed(ctx_embedding, cre_layers, gene_layers, cre_x, gene
             gene = ops.gather_rows_f32(gene_unique[0], gene_unique[1], gene_unique[2])
             gene_x = gene
         kw0 = {} if qkv0 is None else {"self_qkv": qkv0}
-        gene = gene_layers[0].forward_packed(gene, cu_gene_self, max_gene, context=cre, cu_ctx=ck, max_ctx=max_cre,
-                                             cu_cross_q=cq, max_cross_q=mq, keep_x=not t16 or use_res or n == 1, **kw0)
+        with attn_maps.gene_layer(0):
+            gene = gene_layers[0].forward_packed(gene, cu_gene_self, max_gene, context=cre, cu_ctx=ck, max_ctx=max_cre,
+                                                 cu_cross_q=cq, max_cross_q=mq, keep_x=not t16 or use_res or n == 1, **kw0)
     if use_res:                                     # gene-stream input added back after every gene layer (:253-254)
         gene = ops.add_rows(_as_tensor(gene), gene_x)
     log2c = None
@@ -328,10 +329,12 @@ def modulator_forward_packed(ctx_embedding, cre_layers, gene_layers, cre_x, gene
             if final_rows is not None and i == n - 1:
                 # last gene layer: only the registry rows are consumed downstream -> compact [R, D] result
                 rows, cu_rows, cu_cross_rows, max_cross_rows = final_rows
-                return gene_layers[i].forward_packed_rows(gene_in, cu_gene_self, max_gene, rows, cu_rows, cre_i, ck, max_cre,
-                                                          cu_cross_rows, max_cross_rows)
-            g = gene_layers[i].forward_packed(gene_in, cu_gene_self, max_gene, context=cre_i, cu_ctx=ck, max_ctx=max_cre,
-                                              cu_cross_q=cq, max_cross_q=mq, keep_x=not t16 or use_res or i == n - 1)
+                with attn_maps.gene_layer(i, compact=True):       # the query buffer already is the registry rows
+                    return gene_layers[i].forward_packed_rows(gene_in, cu_gene_self, max_gene, rows, cu_rows, cre_i, ck, max_cre,
+                                                              cu_cross_rows, max_cross_rows)
+            with attn_maps.gene_layer(i):
+                g = gene_layers[i].forward_packed(gene_in, cu_gene_self, max_gene, context=cre_i, cu_ctx=ck, max_ctx=max_cre,
+                                                  cu_cross_q=cq, max_cross_q=mq, keep_x=not t16 or use_res or i == n - 1)
             if use_res:                                 # :284-285
                 g = ops.add_rows(_as_tensor(g), gene_x)
             return g
@@ -796,6 +799,12 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
             cre_x = cre_tok.float()
         w, b = packed_linear(self.gene_map)
         gene_x = ops.gemm(gene_tok, w, b, ops.EPI_F32)
+        cap = attn_maps.active()
+        if cap is not None:
+            # the maps' rows are the registry-token rows -- the only rows the expression head reads; pb.registry_rows already
+            # indexes the buffer the gene layers' cross attention projects its queries from (the gene stream itself)
+            self._attention_maps_supported()
+            cap.begin(pb.registry_rows, pb.cu_registry_cross, pb.max_tissues, pb.cu_cre, pb.max_cre)
         if self._general:
             return self._forward_general(pb, cre_x, gene_x, return_cre)
         # registry token per (gene, tissue) + that gene's chunk rows (:357-366, layers.py:508-521)
@@ -937,6 +946,45 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
             return self.variant_prediction(batch)
         with torch.no_grad():
             return self.predict_finish(self.predict_launch(self.prepare_batch(batch)), batch_idx, dataloader_idx)
+
+    def _attention_maps_supported(self) -> None:
+        """Raises NotImplementedError naming the option that has no attention-map capture."""
+        if self.vep:
+            raise NotImplementedError("attention maps: vep models (the ref / het / hom path) are not supported")
+        off = [name for name, on in (("only_cross_attention", self.only_cross_attention), ("use_res", self.use_res),
+                                     ("cross_alibi", self.cross_alibi), ("add_context_to_cres", self.add_context_to_cres),
+                                     (f"gene_pooling={self.gene_pooling!r}", self.gene_pooling != "multi_registry")) if on]
+        if off:
+            raise NotImplementedError("attention maps: not supported with " + ", ".join(off) + " (the per-(gene, tissue) "
+                                      "evaluation order of the options the shipped configuration leaves off)")
+
+    def predict_step_with_attention(self, batch, batch_idx, dataloader_idx=None, layers=None, per_head=False):
+        """predict_step's dict plus the gene -> cCRE attention maps of the same forward:
+          "cre_attention"         per gene, fp32 numpy [len(layers), T_i, N_i] -- the head mean of the softmax of gene layer
+                                  `layers[k]`'s cross attention on the registry-token row of tissue t (tissues in the order of
+                                  tissue_context[i], cCREs in the order of cre_sequences[i]) -- or [len(layers), T_i, H, N_i]
+                                  with per_head;
+          "cre_attention_layers"  the captured gene-layer indices.
+        layers: distinct gene-layer indices (negative: from the end; None: all; ValueError for an index out of range, an empty
+        list or a layer named twice).  When the batch trips the LayerNorm-fold alert the
+        recomputation runs under the capture too and the maps are its maps."""
+        self.eval()
+        self._attention_maps_supported()
+        sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
+        with torch.no_grad(), attn_maps.capture(sel, per_head) as cap:
+            pb = self.prepare_batch(batch)
+            out = self.predict_finish(self.predict_launch(pb), batch_idx, dataloader_idx)
+            maps = cap.maps.detach().cpu().numpy()                # the recomputation's when predict_finish healed the batch
+        H, per_gene, r = self.combined_modulator.num_heads, [], 0
+        for i in range(pb.n_genes):
+            t, nc = len(pb.tissues[i]), pb.n_cre[i]
+            if per_head:
+                per_gene.append(np.ascontiguousarray(maps[:, r * H:(r + t) * H, :nc].reshape(len(sel), t, H, nc)))
+            else:
+                per_gene.append(np.ascontiguousarray(maps[:, r:r + t, :nc]))
+            r += t
+        out["cre_attention"], out["cre_attention_layers"] = per_gene, sel
+        return out
 
     def predict_launch(self, pb: PreparedBatch) -> PredictHandle:
         """Enqueue the forward of a prepared batch; returns without waiting for the GPU (the kernels run on the

@@ -18,7 +18,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from ... import ops, runtime, weights
+from ... import attn_maps, ops, runtime, weights
 
 
 def get_alibi_slopes(n: int) -> torch.Tensor:
@@ -339,7 +339,14 @@ class MHA(nn.Module):
         None: x is the 16-bit operand itself)."""
         D = self.embed_dim
         if self.cross_attn:
-            return ops.attn_varlen(self.project_q(x, norm), kv_bf16[:, :D], kv_bf16[:, D:], cu_q, cu_k, max_q, max_k,
+            q = self.project_q(x, norm)
+            cap = attn_maps.running()          # a requested gene layer's cross attention under attn_maps.capture: its P, in fp32
+            if cap is not None:
+                if self.alibi_slopes is not None:
+                    raise NotImplementedError("attention maps: cross_alibi (a positional bias in the gene -> cCRE cross "
+                                              "attention) has no probabilities kernel")
+                cap.record(q, kv_bf16[:, :D], self.num_heads, self.head_dim, family=self.family)
+            return ops.attn_varlen(q, kv_bf16[:, :D], kv_bf16[:, D:], cu_q, cu_k, max_q, max_k,
                                    self.num_heads, self.head_dim, self.alibi_slopes, family=self.family, q_log2=True)
         return self.attend_qkv(self.project_qkv(x, norm), cu_q, max_q)
 

@@ -283,14 +283,22 @@ class ExtractSeqFromBed:
 
     # -- all CRE windows of a gene ---------------------------------------------------------------------
     def process_subject(self, vcf_file: str, bed_regions: pd.DataFrame, variant_type: str = None):
-        rows = []
-        for region in bed_regions.itertuples(index=False):           # .chrom .start .end .cCRE, as a Series row would
+        """The frame's `attrs["bed_rows"]` names, for every row returned, the position of its region in `bed_regions` (regions
+        without a sequence are dropped, the rest re-ordered below): the one statement of this path's row order, for callers
+        that have to name the rows afterwards (VCFDataset.cre_table)."""
+        rows, kept = [], []
+        for k, region in enumerate(bed_regions.itertuples(index=False)):           # .chrom .start .end .cCRE, as a Series row would
             d, _ = self.process_region((region, vcf_file, self.ref_fasta, variant_type))
             if d:
                 rows.append(d)
+                kept.append(k)
         df = pd.DataFrame(rows, columns=["chrom", "start_cre", "end_cre", "sequence", "cCRE"])
+        kept = np.asarray(kept, dtype=np.int64)
         if len(df) and not df["start_cre"].is_monotonic_increasing:
-            df = df.sort_values(by=["chrom", "start_cre"], ascending=True).reset_index(drop=True)
+            df = df.sort_values(by=["chrom", "start_cre"], ascending=True)
+            kept = kept[df.index.to_numpy()]
+            df = df.reset_index(drop=True)
+        df.attrs["bed_rows"] = kept
         return df
 
     # -- gene body -------------------------------------------------------------------------------------
