@@ -276,6 +276,32 @@ int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int64_t k_stri
                   int operand_dtype, int flags, int per_head,
                   float* stats, float* out, int64_t ldo, void* stream);
 
+/* vf_attn_probs with a positional bias and a row map for the keys (added under ABI 13: a new symbol, vf_attn_probs keeps its
+ * bits and is this entry with the three new pointers NULL, so the version stays 13).  For the gene-body attention maps: the
+ * registry token's SELF attention over its own sequence (registry token + gene-body chunks, ALiBi).
+ * Arguments, semantics and refusals of vf_attn_probs, plus three optional device pointers:
+ *   alibi_slopes  fp32 [H].  The base-2 logit becomes c * (q . k) - log2(e) * alibi_slopes[h] * |q_pos[r] - j|, c = 1
+ *                 (VF_ATTN_Q_LOG2) or scale * log2(e), j = the key's position inside its sequence: one fp32 fma on the fp32
+ *                 MFMA accumulator, before the maximum.  After that the contract is vf_attn_probs's: m is the true maximum of
+ *                 the biased logits, P = exp2(s2 - m) / l, nothing rounded to 16 bits, no atomics; the bits of a row depend on
+ *                 its own query, keys, position and the slopes alone.
+ *   q_pos         int32 [R]: the position of selected row r inside its key sequence.  NULL = 0 for every row (the registry
+ *                 token).  Ignored without alibi_slopes.  One explicit position replaces the two alignment conventions of the
+ *                 forward entries: VF_ATTN_Q_AT_START stays refused.  Not checked: a negative or out-of-range position is
+ *                 simply the distance it implies.
+ *   k_rows        int64 [cu_seqlens_k[n_seq]]: key j of sequence s is row k_rows[cu_seqlens_k[s] + j] of k (rows may repeat;
+ *                 the row-map form of vf_attn_varlen_fwd_rows).  The arithmetic is that of a call on the gathered rows:
+ *                 bit-identical.  Every entry must name a row of k; not checked.
+ * Non-finite operands as for vf_attn_probs; in addition a NaN in alibi_slopes[h] makes head h NaN in every row that has keys
+ * (per_head: no other head; the head mean of those rows is NaN).  The three pointers must be aligned to their element size.
+ * vf_last_kernel(1) is "attn_probs_alibi_kernel" with alibi_slopes, "attn_probs_kernel" without. */
+int vf_attn_probs_v2(const void* q, int64_t q_stride, const void* k, int64_t k_stride,
+                     const int64_t* q_rows, const int32_t* cu_rows, const int32_t* cu_seqlens_k,
+                     int n_seq, int max_rows, int max_seqlen_k, int H, int dh, float scale,
+                     int operand_dtype, int flags, int per_head,
+                     float* stats, float* out, int64_t ldo,
+                     const float* alibi_slopes, const int32_t* q_pos, const int64_t* k_rows, void* stream);
+
 /* The same attention in LOW-RANK form (ABI 10): with C distinct key / value rows per head the logits are
  * LN(x) . (Wq_h^T k_c) -- vf_gemm_ln as a CONSUMER with fp32 output (epilogue VF_EPI_F32, new in ABI 10) against an
  * [H * Cp, D] matrix built once per weights -- and out_proj(sum_c w_c v_c) is w . (Wo_h v_c), a GEMM with K = H * Cp (Cp >= C,

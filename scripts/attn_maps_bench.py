@@ -1,7 +1,8 @@
-"""What the gene -> cCRE attention maps cost at the headline shape (bench.py's model and batch: 32 genes x 54 tissues,
-1024 cCREs, production depth): step time with the capture off, with the last gene layer only, with all gene layers, and the
-probabilities kernel's own time and its algorithmic bytes / time against the HBM peak (ops.KernelTimer).  One JSON line, also written to
-profiles/attn_maps_bench.json.
+"""What the attention maps cost at the headline shape (bench.py's model and batch: 32 genes x 54 tissues, 1024 cCREs,
+production depth): step time with the capture off, with the gene -> cCRE maps of the last gene layer only and of all gene
+layers, with BOTH maps (gene -> cCRE and gene body) of the last layer and of all layers, and the two probabilities kernels' own
+times and algorithmic bytes / time against the HBM peak (ops.KernelTimer).  One JSON line, also written to
+profiles/attn_maps_bench_gene_body.json (profiles/attn_maps_bench.json is the run before the gene-body maps existed).
 
     python scripts/attn_maps_bench.py [--steps 6] [--warmup 3] [--genes-per-step 32] [--layers N]
 
@@ -31,7 +32,7 @@ def main():
     ap.add_argument("--n-chunks", type=int, default=200)
     ap.add_argument("--tissues", type=int, default=54)
     ap.add_argument("--layers", type=int, default=None, help="override modulator depth (debug only)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "attn_maps_bench.json"))
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "attn_maps_bench_gene_body.json"))
     args = ap.parse_args()
 
     import bench
@@ -44,15 +45,17 @@ def main():
     batch = make_batch(20251205, [args.n_cre] * G, [args.n_chunks] * G, [tissues] * G, 200)
     n_layers = len(model.combined_modulator.gene_layers)
 
-    def timed(layers, d2h):
+    def timed(layers, d2h, gene_body=False):
         def step():
             if layers is None:
                 model.forward_prepared(pb)[0].cpu()
                 return
-            with attn_maps.capture(layers) as cap:
+            with attn_maps.capture(layers, gene_body=gene_body) as cap:
                 model.forward_prepared(pb)[0].cpu()
                 if d2h:
                     cap.maps.cpu()
+                    if gene_body:
+                        cap.gene_maps.cpu()
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
@@ -69,20 +72,28 @@ def main():
         last_d2h = timed([n_layers - 1], True)
         every = timed(list(range(n_layers)), False)
         every_d2h = timed(list(range(n_layers)), True)
+        both_last = timed([n_layers - 1], False, True)
+        both_last_d2h = timed([n_layers - 1], True, True)
+        both_every = timed(list(range(n_layers)), False, True)
+        both_every_d2h = timed(list(range(n_layers)), True, True)
         off_again = timed(None, False)
         ops.TIMER = ops.KernelTimer()
-        with attn_maps.capture(list(range(n_layers))):
+        with attn_maps.capture(list(range(n_layers)), gene_body=True):
             model.forward_prepared(pb)[0].cpu()
         summ = ops.TIMER.summary()
         ops.TIMER = None
     k = summ["attn_probs"]
     gbs = k["bytes"] / (k["total_ms"] * 1e-3) / 1e9
+    ka = summ["attn_probs_alibi"]
+    gbs_a = ka["bytes"] / (ka["total_ms"] * 1e-3) / 1e9
     result = {
         "shape": {"genes": G, "tissues": len(tissues), "n_cre": args.n_cre, "n_chunks": args.n_chunks, "gene_layers": n_layers},
         "steps": args.steps, "warmup": args.warmup,
         "capture_off_ms": round(off, 3), "capture_off_repeat_ms": round(off_again, 3),
         "last_layer_ms": round(last, 3), "last_layer_with_d2h_ms": round(last_d2h, 3),
         "all_layers_ms": round(every, 3), "all_layers_with_d2h_ms": round(every_d2h, 3),
+        "both_maps_last_layer_ms": round(both_last, 3), "both_maps_last_layer_with_d2h_ms": round(both_last_d2h, 3),
+        "both_maps_all_layers_ms": round(both_every, 3), "both_maps_all_layers_with_d2h_ms": round(both_every_d2h, 3),
         "kernel": {"launches": k["launches"], "total_ms": round(k["total_ms"], 3),
                    "ms_per_layer": round(k["total_ms"] / k["launches"], 4), "bytes": k["bytes"], "flops": k["flops"],
                    "algorithmic_gb_per_s": round(gbs, 1), "algorithmic_gb_per_s_over_hbm_peak": round(gbs / HBM_PEAK_GBS, 4),
@@ -91,6 +102,13 @@ def main():
                            "once), so the rate is algorithmic bytes / time, not traffic measured at the HBM: pass 1 reads K once "
                            "per 32-row tile (twice at 54 rows) and a K slab that fits the last-level cache need not come from "
                            "HBM in pass 2"},
+        "kernel_alibi": {"launches": ka["launches"], "total_ms": round(ka["total_ms"], 3),
+                         "ms_per_layer": round(ka["total_ms"] / ka["launches"], 4), "bytes": ka["bytes"], "flops": ka["flops"],
+                         "algorithmic_gb_per_s": round(gbs_a, 1), "algorithmic_gb_per_s_over_hbm_peak": round(gbs_a / HBM_PEAK_GBS, 4),
+                         "note": "the gene-body map's launches (ALiBi form of vf_attn_probs_v2, one registry row per (gene, "
+                                 "tissue) against its <= 201 keys).  bytes = the selected queries twice, every sequence's K once "
+                                 "per pass, the index loads (q_rows; in the first layer also the key row map), the map and the "
+                                 "statistics"},
         "source_sha": bench.source_sha(),
     }
     line = json.dumps(result)

@@ -45,6 +45,7 @@ SIGNATURES = {
     "vf_attn_rows_supported": [_i, _i, _i, _i, _i, _i, _i],
     "vf_attn_counted_keys": [_p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],
     "vf_attn_probs": [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p, _l, _p],
+    "vf_attn_probs_v2": [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p, _l, _p, _p, _p, _p],
     "vf_softmax_counted": [_p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],
     "vf_attn_varlen_fwd_rows": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p, _p, _p],
     "vf_layernorm": [_p, _p, _p, _p, _l, _i, _f, _i, _i, _p],

@@ -1,4 +1,6 @@
-"""Gene -> cCRE attention maps: the sink the gene layers' cross attention writes its softmax probabilities into.
+"""Attention maps of the registry tokens: the sink the gene layers write their softmax probabilities into -- the cross
+attention over the gene's cCREs (`maps`) and, with gene_body=True, the self attention over the token's own sequence, the
+registry token and the gene-body chunks behind it (`gene_maps`).
 
 Held in a context variable like runtime.Switches (no module globals; `with` blocks nest and restore; a thread starts
 without a capture), so a capture requested around one model's forward never reaches another thread's.  Off unless a
@@ -7,10 +9,12 @@ without a capture), so a capture requested around one model's forward never reac
     with attn_maps.capture(layers=(0, 24), per_head=False) as cap:
         model.forward_prepared(pb)            # or predict_launch / predict_finish
     cap.maps                                  # fp32 [len(layers), sum T (* H), max_cre], row r = row r of `emb`
+    cap.gene_maps                             # gene_body=True: fp32 [len(layers), sum T (* H), max_gene], column 0 = the token itself
 
 Who calls what: the model's forward `begin`s the capture with the batch's selected rows (the registry-token rows, the
 only rows the expression head reads); modulator_forward_packed wraps every GENE layer in `cap.layer(i, ...)`; MHA.attend's
-cross branch asks `running()` and, inside a requested gene layer only, hands q and K to `record`.  The CRE layers run
+cross branch asks `running()` and, inside a requested gene layer only, hands q and K to `record`; MHA.attend_qkv and the last
+layer's forward_packed_rows hand the self attention's q and K to `record_self` at the same places.  The CRE layers run
 outside any `layer(...)` block and are never captured.  DESIGN.md section 5b.
 """
 from __future__ import annotations
@@ -25,23 +29,31 @@ _CAP: contextvars.ContextVar = contextvars.ContextVar("vf_attn_capture", default
 
 
 class Capture:
-    def __init__(self, layers, per_head: bool = False):
+    def __init__(self, layers, per_head: bool = False, gene_body: bool = False):
         self.layers = tuple(int(i) for i in layers)     # distinct gene-layer indices, in the order of the first axis of `maps`
         if not self.layers or len(set(self.layers)) != len(self.layers):
             raise ValueError(f"attention maps: a capture needs distinct gene layers, got {list(self.layers)}")
         self.per_head = bool(per_head)
+        self.gene_body = bool(gene_body)
         self.maps = None          # fp32 [len(layers), R or R * H, max_k] of the most recent forward
+        self.gene_maps = None     # gene_body: fp32 [len(layers), R or R * H, max_gene] of the most recent forward
+        self.shape = None         # the forward's (tissues, cCREs, chunks) per gene: how the rows and columns split (host lists)
+        self._self = None         # (cu_rows int32 [n_seq + 1], cu_k int32 [n_seq + 1], max_k): the self-attention grouping
         self.n_rows = 0
         self._rows = None         # (q_rows int64 [R], cu_rows int32 [n_seq + 1], max_rows, cu_k int32 [n_seq + 1], max_k)
         self._running = None      # (slot in `layers`, compact: the query buffer holds exactly the selected rows)
 
-    def begin(self, q_rows, cu_rows, max_rows: int, cu_k, max_k: int) -> None:
+    def begin(self, q_rows, cu_rows, max_rows: int, cu_k, max_k: int, gene_self=None, shape=None) -> None:
         """A forward starts: its selected rows (row q_rows[r] of the gene layers' query buffer, grouped per key sequence by
-        cu_rows) and keys.  The buffers are the forward's own: a second forward under the same capture (the LayerNorm-fold
-        recomputation) starts afresh and `maps` is then its result."""
+        cu_rows) and keys.  gene_self = (cu_rows, cu_k, max_k): the same rows grouped per SELF-attention sequence and those
+        sequences' keys (every selected row sits at position 0 of its sequence).  The buffers are the forward's own: a second
+        forward under the same capture (the LayerNorm-fold recomputation) starts afresh and the maps are then its result."""
         self._rows = (q_rows, cu_rows, int(max_rows), cu_k, int(max_k))
+        self._self = None if gene_self is None else (gene_self[0], gene_self[1], int(gene_self[2]))
         self.n_rows = int(q_rows.numel())
+        self.shape = shape
         self.maps = None
+        self.gene_maps = None
 
     def layer(self, i: int, compact: bool = False):
         """with cap.layer(i): gene layer i is running.  compact: its cross attention's query buffer already is the selected rows,
@@ -58,6 +70,24 @@ class Capture:
             assert q.shape[0] == self.n_rows
         ops.attn_probs(q, k, cu_rows, cu_k, max_rows, max_k, n_heads, head_dim, q_rows=None if compact else q_rows,
                        q_log2=True, per_head=self.per_head, out=self.maps[slot], family=family + "_maps")
+
+
+    def record_self(self, q, k, n_heads: int, head_dim: int, slopes=None, rows=None, family: str = "") -> None:
+        """The running gene layer's SELF attention: q / k its 16-bit query and key operands, slopes its ALiBi slopes (None: a
+        model built without), rows int64 [tokens]: q and k are a table of distinct projected rows and token t's row is
+        rows[t] (the first gene layer).  The selected rows are registry tokens: position 0 of their sequences."""
+        slot, compact = self._running
+        cu_rows, cu_k, max_k = self._self
+        q_rows = None if compact else self._rows[0]
+        n_out = self.n_rows * (n_heads if self.per_head else 1)
+        if self.gene_maps is None:
+            self.gene_maps = torch.empty((len(self.layers), n_out, max_k), dtype=torch.float32, device=q.device)
+        if compact:
+            assert q.shape[0] == self.n_rows and rows is None
+        elif rows is not None:
+            q_rows = rows[q_rows]
+        ops.attn_probs(q, k, cu_rows, cu_k, 1, max_k, n_heads, head_dim, q_rows=q_rows, q_log2=True, per_head=self.per_head,
+                       out=self.gene_maps[slot], family=family + "_maps", slopes=slopes, q_pos=None, k_rows=rows)
 
 
 class _Layer:
@@ -118,11 +148,18 @@ def running() -> Capture | None:
     return cap if cap is not None and cap._running is not None and cap._rows is not None else None
 
 
-class capture:
-    """with attn_maps.capture(layers, per_head) as cap: every forward inside records the requested gene layers' maps."""
+def running_self() -> Capture | None:
+    """running(), when the capture also asked for the gene-body maps and its forward has named the self-attention grouping."""
+    cap = running()
+    return cap if cap is not None and cap.gene_body and cap._self is not None else None
 
-    def __init__(self, layers, per_head: bool = False):
-        self.cap = Capture(layers, per_head)
+
+class capture:
+    """with attn_maps.capture(layers, per_head, gene_body) as cap: every forward inside records the requested gene layers'
+    maps (gene_body: also those of the self attention over the gene body)."""
+
+    def __init__(self, layers, per_head: bool = False, gene_body: bool = False):
+        self.cap = Capture(layers, per_head, gene_body)
 
     def __enter__(self) -> Capture:
         self.token = _CAP.set(self.cap)

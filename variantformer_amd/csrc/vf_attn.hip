@@ -1755,7 +1755,11 @@ extern "C" int vf_attn_varlen_fwd_rows(const void* q, const void* k, const void*
 
 // ---------------------------------------------------------------------------------------------------------------------
 // vf_attn_probs: the softmax PROBABILITIES of a few selected query rows against their sequence's keys, in fp32 -- the quantity
-// the flash-style kernels above keep in registers, round to 16 bits for P . V and never write.  No V, no positional bias.
+// the flash-style kernels above keep in registers, round to 16 bits for P . V and never write.  No V.  vf_attn_probs_v2 adds
+// ALiBi (template parameter ALIBI: base-2 logit c (q . k) - log2(e) slope[h] |q_pos[r] - j|, one fma on the fp32 accumulator
+// before the maximum, q_pos an explicit position per selected row) and a row map for the keys (template parameter KROWS: key j of
+// sequence s is row k_rows[cu_k[s] + j] of k); the <false, false> instantiations are vf_attn_probs's kernels, instruction for
+// instruction.
 // Same MFMA formulation as attn_x32_kernel (v_mfma_f32_32x32x16, S^T[key 32][query 32] = K . Q^T, A = 32 key rows, B = Q^T;
 // lane (query = lane & 31, hf = lane >> 5) ends up with keys (i & 3) + 8 (i >> 2) + 4 hf of ITS query in register i), but the
 // fragments come straight from global memory: a few dozen rows against 10^3 keys is T * N * D MACs per sequence, two waves at
@@ -1790,6 +1794,9 @@ struct ProbsParams {
     float* stats;
     float* out;
     int64_t ldo;
+    const float* slopes;        // ALIBI: fp32 [H]
+    const int32_t* q_pos;       // ALIBI: position of selected row r inside its key sequence; null: 0
+    const int64_t* k_rows;      // KROWS: key j of sequence s is row k_rows[cu_k[s] + j] of k
 };
 
 template <int DT, int KS>
@@ -1801,20 +1808,26 @@ __device__ __forceinline__ void probs_load_frags(typename Op16<DT>::frag (&f)[KS
     }
 }
 
-// base-2 logits of one 32-key x 32-query tile; keys at or past `klim` (relative to the tile's first key) are -inf
-template <int DT, int KS>
+// base-2 logits of one 32-key x 32-query tile; keys at or past `klim` (relative to the tile's first key) are -inf.
+// ALIBI: slope2 = log2(e) * slope[h], dq = the lane's query position minus the tile's first key (a small integer: dq - key is
+// exact); both passes go through this one function, so they add the same bias with the same two instructions.
+template <int DT, int KS, bool ALIBI>
 __device__ __forceinline__ void probs_logits(const typename Op16<DT>::frag (&kf)[KS], const typename Op16<DT>::frag (&qf)[KS],
-                                             float c, int klim, int hf, float (&s)[16]) {
+                                             float c, int klim, int hf, float slope2, float dq, float (&s)[16]) {
     f32x16_t acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) acc = Op16<DT>::mfma32(kf[ks], qf[ks], acc);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) s[i] = ((i & 3) + 8 * (i >> 2) + 4 * hf) < klim ? acc[i] * c : -INFINITY;
+    for (int i = 0; i < 16; ++i) {
+        const int key = (i & 3) + 8 * (i >> 2) + 4 * hf;
+        if constexpr (ALIBI) s[i] = key < klim ? __builtin_fmaf(acc[i], c, -slope2 * __builtin_fabsf(dq - (float)key)) : -INFINITY;
+        else s[i] = key < klim ? acc[i] * c : -INFINITY;
+    }
 }
 
-template <int DT, int DH>
+template <int DT, int DH, bool ALIBI, bool KROWS>
 __global__ __launch_bounds__(256) void attn_probs_stats_kernel(ProbsParams P) {
     using frag_t = typename Op16<DT>::frag;
     constexpr int KS = DH / 16;
@@ -1836,14 +1849,16 @@ __global__ __launch_bounds__(256) void attn_probs_stats_kernel(ProbsParams P) {
     const int64_t q_row = P.q_rows ? P.q_rows[r] : (int64_t)r;
     frag_t qf[KS];
     probs_load_frags<DT, KS>(qf, P.q + q_row * P.q_stride + h * DH + 8 * hf);
-    const unsigned short* kp = P.k + (int64_t)k0 * P.k_stride + h * DH + 8 * hf;
+    const unsigned short* kp = P.k + (KROWS ? (int64_t)0 : (int64_t)k0 * P.k_stride) + h * DH + 8 * hf;
+    const float slope2 = ALIBI ? P.slopes[h] * 1.4426950408889634f : 0.f;
+    const int qpos = ALIBI && P.q_pos ? P.q_pos[r] : 0;
     float m = -INFINITY, l = 0.f;
     for (int kb = 0; kb < len_k; kb += 32) {
         const int key = kb + x < len_k ? kb + x : len_k - 1;    // in bounds; the logit is masked below
         frag_t kf[KS];
-        probs_load_frags<DT, KS>(kf, kp + (int64_t)key * P.k_stride);
+        probs_load_frags<DT, KS>(kf, kp + (KROWS ? P.k_rows[k0 + key] : (int64_t)key) * P.k_stride);
         float s[16];
-        probs_logits<DT, KS>(kf, qf, P.c, len_k - kb, hf, s);
+        probs_logits<DT, KS, ALIBI>(kf, qf, P.c, len_k - kb, hf, slope2, (float)(qpos - kb), s);
         float mx = s[0];
 #pragma unroll
         for (int i = 1; i < 16; ++i) mx = max2f(mx, s[i]);
@@ -1871,7 +1886,7 @@ __device__ __forceinline__ void probs_store4(float* op, int col, int max_k, f32x
     }
 }
 
-template <int DT, int DH>
+template <int DT, int DH, bool ALIBI, bool KROWS>
 __global__ __launch_bounds__(256) void attn_probs_kernel(ProbsParams P) {
     using frag_t = typename Op16<DT>::frag;
     constexpr int KS = DH / 16;
@@ -1902,7 +1917,8 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(ProbsParams P) {
     }
 
     const int key = x < klim ? kbase + x : len_k - 1;
-    const unsigned short* kp = P.k + (int64_t)(k0 + key) * P.k_stride + 8 * hf;
+    const unsigned short* kp = P.k + (KROWS ? P.k_rows[k0 + key] : (int64_t)(k0 + key)) * P.k_stride + 8 * hf;
+    const float dq = (float)((ALIBI && P.q_pos ? P.q_pos[r] : 0) - kbase);
     const int64_t q_row = P.q_rows ? P.q_rows[r] : (int64_t)r;
     const unsigned short* qp = P.q + q_row * P.q_stride + 8 * hf;
     const float* sp = P.stats + (int64_t)r * H * 2;
@@ -1915,15 +1931,17 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(ProbsParams P) {
     probs_load_frags<DT, KS>(kf, kp);
     probs_load_frags<DT, KS>(qf, qp);
     float m = sp[0], l = sp[1];
+    float slope = ALIBI ? P.slopes[0] : 0.f;
     for (int h = 0; h < H; ++h) {
         const int hn = h + 1 < H ? h + 1 : h;
         frag_t kn[KS], qn[KS];
         probs_load_frags<DT, KS>(kn, kp + hn * DH);
         probs_load_frags<DT, KS>(qn, qp + hn * DH);
         const float m_n = sp[2 * hn], l_n = sp[2 * hn + 1];
+        const float slope_n = ALIBI ? P.slopes[hn] : 0.f;
 
         float s[16];
-        probs_logits<DT, KS>(kf, qf, P.c, klim, hf, s);
+        probs_logits<DT, KS, ALIBI>(kf, qf, P.c, klim, hf, slope * 1.4426950408889634f, dq, s);
         const float inv = 1.0f / l;
         float p[16];
 #pragma unroll
@@ -1942,7 +1960,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(ProbsParams P) {
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) { kf[ks] = kn[ks]; qf[ks] = qn[ks]; }
-        m = m_n; l = l_n;
+        m = m_n; l = l_n; slope = slope_n;
     }
     if (!P.per_head && row_ok) {
         const float inv_h = 1.0f / (float)H;
@@ -1954,27 +1972,36 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(ProbsParams P) {
     }
 }
 
-template <int DT, int DH>
+template <int DT, int DH, bool ALIBI, bool KROWS>
 static int launch_attn_probs(const ProbsParams& P, int max_rows, hipStream_t st) {
     const long waves = (long)P.n_seq * P.nrt * P.H;
-    hipLaunchKernelGGL((attn_probs_stats_kernel<DT, DH>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, P);
+    hipLaunchKernelGGL((attn_probs_stats_kernel<DT, DH, ALIBI, KROWS>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, P);
     VF_CHECK_LAUNCH("vf_attn_probs");
     if (P.max_k > 0) {
-        hipLaunchKernelGGL((attn_probs_kernel<DT, DH>), dim3((P.max_k + 63) / 64, (max_rows + 63) / 64, P.n_seq), dim3(256), 0, st, P);
+        hipLaunchKernelGGL((attn_probs_kernel<DT, DH, ALIBI, KROWS>), dim3((P.max_k + 63) / 64, (max_rows + 63) / 64, P.n_seq),
+                           dim3(256), 0, st, P);
         VF_CHECK_LAUNCH("vf_attn_probs");
     }
     return VF_OK;
 }
 
+template <int DT, int DH>
+static int launch_attn_probs_form(const ProbsParams& P, int max_rows, hipStream_t st) {
+    if (P.slopes) return P.k_rows ? launch_attn_probs<DT, DH, true, true>(P, max_rows, st) : launch_attn_probs<DT, DH, true, false>(P, max_rows, st);
+    return P.k_rows ? launch_attn_probs<DT, DH, false, true>(P, max_rows, st) : launch_attn_probs<DT, DH, false, false>(P, max_rows, st);
+}
+
 }  // namespace
 
-extern "C" int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int64_t k_stride, const int64_t* q_rows,
-                             const int32_t* cu_rows, const int32_t* cu_seqlens_k, int n_seq, int max_rows, int max_seqlen_k, int H,
-                             int dh, float scale, int operand_dtype, int flags, int per_head, float* stats, float* out, int64_t ldo,
-                             void* stream) {
-    VF_REQUIRE(q && k && cu_rows && cu_seqlens_k && stats && out, "vf_attn_probs: null pointer");
+extern "C" int vf_attn_probs_v2(const void* q, int64_t q_stride, const void* k, int64_t k_stride, const int64_t* q_rows,
+                                const int32_t* cu_rows, const int32_t* cu_seqlens_k, int n_seq, int max_rows, int max_seqlen_k,
+                                int H, int dh, float scale, int operand_dtype, int flags, int per_head, float* stats, float* out,
+                                int64_t ldo, const float* alibi_slopes, const int32_t* q_pos, const int64_t* k_rows, void* stream) {
+    const char* null_arg = !q ? "q" : !k ? "k" : !cu_rows ? "cu_rows" : !cu_seqlens_k ? "cu_seqlens_k" : !stats ? "stats" : !out ? "out" : nullptr;
+    VF_REQUIRE(!null_arg, "vf_attn_probs: null pointer %s", null_arg);
     VF_REQUIRE(operand_dtype == VF_BF16 || operand_dtype == VF_F16, "vf_attn_probs: operand_dtype must be VF_BF16 or VF_F16");
-    VF_REQUIRE((flags & ~VF_ATTN_Q_LOG2) == 0, "vf_attn_probs: flags 0x%x: only VF_ATTN_Q_LOG2 applies (no positional bias)", flags);
+    VF_REQUIRE((flags & ~VF_ATTN_Q_LOG2) == 0, "vf_attn_probs: flags 0x%x: only VF_ATTN_Q_LOG2 applies (VF_ATTN_Q_AT_START is "
+               "refused: q_pos names every row's position)", flags);
     VF_REQUIRE(legacy_dh(dh), "vf_attn_probs: head_dim %d not supported (32/48/64/96/128)", dh);
     VF_REQUIRE(H > 0 && H <= 65535 && n_seq >= 0 && max_rows >= 0 && max_seqlen_k >= 0,
                "vf_attn_probs: H=%d n_seq=%d max_rows=%d max_seqlen_k=%d out of range", H, n_seq, max_rows, max_seqlen_k);
@@ -1983,6 +2010,8 @@ extern "C" int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int
     VF_REQUIRE(q_stride % 8 == 0 && k_stride % 8 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) &&
                    ((uintptr_t)stats % 4 == 0) && ((uintptr_t)out % 4 == 0),
                "vf_attn_probs: q / k rows must keep 16-byte alignment");
+    VF_REQUIRE(((uintptr_t)alibi_slopes % 4 == 0) && ((uintptr_t)q_pos % 4 == 0) && ((uintptr_t)k_rows % 8 == 0),
+               "vf_attn_probs: alibi_slopes / q_pos / k_rows are not aligned to their element size");
     if (n_seq == 0 || max_rows == 0) return VF_OK;
     const int nrt = (max_rows + 31) / 32;
     VF_REQUIRE(n_seq <= 65535 && (max_rows + 63) / 64 <= 65535 && ((long)n_seq * nrt * H + 3) / 4 < (1L << 31),
@@ -1993,11 +2022,20 @@ extern "C" int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int
     P.c = (flags & VF_ATTN_Q_LOG2) ? 1.0f : scale * 1.4426950408889634f;
     P.H = H; P.n_seq = n_seq; P.nrt = nrt; P.max_k = max_seqlen_k; P.per_head = per_head ? 1 : 0;
     P.stats = stats; P.out = out; P.ldo = ldo;
+    P.slopes = alibi_slopes; P.q_pos = alibi_slopes ? q_pos : nullptr; P.k_rows = k_rows;
     hipStream_t st = (hipStream_t)stream;
-    vf_note_kernel(1, "attn_probs_kernel");
-#define VF_PR(DT_) (dh == 32 ? launch_attn_probs<DT_, 32>(P, max_rows, st) : dh == 48 ? launch_attn_probs<DT_, 48>(P, max_rows, st) : \
-                    dh == 64 ? launch_attn_probs<DT_, 64>(P, max_rows, st) : dh == 96 ? launch_attn_probs<DT_, 96>(P, max_rows, st) : \
-                    launch_attn_probs<DT_, 128>(P, max_rows, st))
+    vf_note_kernel(1, alibi_slopes ? "attn_probs_alibi_kernel" : "attn_probs_kernel");
+#define VF_PR(DT_) (dh == 32 ? launch_attn_probs_form<DT_, 32>(P, max_rows, st) : dh == 48 ? launch_attn_probs_form<DT_, 48>(P, max_rows, st) : \
+                    dh == 64 ? launch_attn_probs_form<DT_, 64>(P, max_rows, st) : dh == 96 ? launch_attn_probs_form<DT_, 96>(P, max_rows, st) : \
+                    launch_attn_probs_form<DT_, 128>(P, max_rows, st))
     return operand_dtype == VF_BF16 ? VF_PR(VF_BF16) : VF_PR(VF_F16);
 #undef VF_PR
+}
+
+extern "C" int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int64_t k_stride, const int64_t* q_rows,
+                             const int32_t* cu_rows, const int32_t* cu_seqlens_k, int n_seq, int max_rows, int max_seqlen_k, int H,
+                             int dh, float scale, int operand_dtype, int flags, int per_head, float* stats, float* out, int64_t ldo,
+                             void* stream) {
+    return vf_attn_probs_v2(q, q_stride, k, k_stride, q_rows, cu_rows, cu_seqlens_k, n_seq, max_rows, max_seqlen_k, H, dh, scale,
+                            operand_dtype, flags, per_head, stats, out, ldo, nullptr, nullptr, nullptr, stream);
 }

@@ -288,15 +288,55 @@ class VCFDataset(Dataset):
         return (torch.from_numpy(X), torch.from_numpy(masks.view(np.bool_)), torch.from_numpy(ref_labels),
                 torch.from_numpy(labels))
 
-    def _get_gene(self, gene_id: str, gene_info: dict, vcf_path: str):
+    def _gene_tokens(self, gene_id: str, gene_info: dict, vcf_path: str, with_starts: bool = False):
+        """(length of the gene body's consensus, its tokens): the strand-oriented consensus encoded as the sample holds it;
+        with_starts: the tokens are (ids, start offset of every token in that oriented sequence).  ONE statement of what is
+        encoded, for _get_gene and gene_chunk_table."""
         seq = self._extractor(self.gene_downstream_neighbour_hood, self.gene_upstream_neighbour_hood).process_gene(
             gene_info, vcf_path)
         assert len(seq) > 1000, f"Mutated sequence is less than 1000bp for gene {gene_id}"
         # only max_chunks x max_length tokens are kept (chunkify_data): the exact prefix of the full encoding (vf_bpe_encode_prefix)
         # -- a 301 kb gene body is ~83 k tokens of which 40 k survive; round 6: 14 -> 8 ms of a gene's 39 ms on the host
-        ids = self.bpe.encode_forward(seq if gene_info["strand"] == "+" else reverse_complement(seq),
-                                      max_tokens=self.max_chunks * self.max_length)
+        return len(seq), self.bpe.encode_forward(seq if gene_info["strand"] == "+" else reverse_complement(seq),
+                                                 max_tokens=self.max_chunks * self.max_length, with_starts=with_starts)
+
+    def _get_gene(self, gene_id: str, gene_info: dict, vcf_path: str):
+        ids = self._gene_tokens(gene_id, gene_info, vcf_path)[1]
         return self.chunkify_data(torch.from_numpy(ids.astype(np.int64)).unsqueeze(0))
+
+    def gene_chunk_table(self, gene_id: str, vcf_path: str = None) -> pd.DataFrame:
+        """One row per gene-body chunk, in the order _get_gene emits them (what names columns 1 .. C of a gene-body attention
+        map; column 0 is the registry token): `chunk`, `tokens` (un-padded), `seq_start` / `seq_end` -- the half-open span of the
+        chunk's tokens in the strand-oriented consensus sequence that was encoded (from the encoder's own token starts) -- and
+        `start` / `end`, the 0-based half-open genomic span on the plus strand.  The genomic span is given only when the
+        consensus has the length of the reference interval (SNPs only); an indel shifts everything behind it, and both columns
+        are then null.  vcf_path: default the query's (cre_table)."""
+        from ..utils.data_process import open_fasta
+        if vcf_path is None:
+            vcf_path = self.vcf_path
+            if "vcf_path" in self.query_df.columns:
+                hit = self.query_df.loc[self.query_df["gene_id"] == gene_id, "vcf_path"]
+                vcf_path = hit.iloc[0] if len(hit) else vcf_path
+        gene_info = self._get_gene_info(gene_id)
+        n_seq, (ids, starts) = self._gene_tokens(gene_id, gene_info, vcf_path, with_starts=True)
+        n_chunks = self.chunkify_data(torch.from_numpy(ids.astype(np.int64)).unsqueeze(0))[0].shape[0]
+        ids, starts = ids[: n_chunks * self.max_length], starts[: n_chunks * self.max_length]
+        ends = starts + np.array([len(self.bpe.id_to_token[int(v)]) for v in ids], dtype=np.int64)
+        first = np.arange(0, len(ids), self.max_length)
+        last = np.minimum(first + self.max_length, len(ids)) - 1
+        table = pd.DataFrame({"chunk": np.arange(len(first)), "tokens": last - first + 1,
+                              "seq_start": starts[first], "seq_end": ends[last]})
+        assert len(table) == n_chunks
+        lo, hi = self._extractor(self.gene_downstream_neighbour_hood, self.gene_upstream_neighbour_hood).gene_region(
+            gene_info["strand"], gene_info["start"], int(gene_info["end"]))
+        hi = min(hi, open_fasta(self.fasta_path).length(gene_info["chromosome"]))
+        if n_seq == hi - lo:
+            plus = gene_info["strand"] == "+"
+            table["start"] = lo + table["seq_start"] if plus else hi - table["seq_end"]
+            table["end"] = lo + table["seq_end"] if plus else hi - table["seq_start"]
+        else:
+            table["start"] = table["end"] = pd.array([pd.NA] * len(table), dtype="Int64")
+        return table
 
     def _load_file(self, idx: int):
         row = self.query_df.iloc[idx]

@@ -534,13 +534,18 @@ def attn_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_q: torch.T
 
 def attn_probs(q: torch.Tensor, k: torch.Tensor, cu_rows: torch.Tensor, cu_k: torch.Tensor, max_rows: int, max_k: int,
                n_heads: int, head_dim: int, q_rows: torch.Tensor | None = None, q_log2: bool = True, per_head: bool = False,
-               scale: float | None = None, out: torch.Tensor | None = None, family: str = ""):
-    """fp32 softmax probabilities of selected query rows against their sequence's keys (vf_attn_probs; attention maps).
+               scale: float | None = None, out: torch.Tensor | None = None, family: str = "",
+               slopes: torch.Tensor | None = None, q_pos: torch.Tensor | None = None, k_rows: torch.Tensor | None = None):
+    """fp32 softmax probabilities of selected query rows against their sequence's keys (vf_attn_probs_v2; attention maps).
     q [*, >=H*dh] / k [tk, >=H*dh] 16-bit row-strided views; selected row r (cu_rows int32 [n_seq + 1] groups them per key
     sequence) is row q_rows[r] of q (int64; None: row r, and q holds exactly the selected rows).  Returns (out, stats):
     out fp32 [R, max_k] = the head mean, or [R * H, max_k] per head (columns past a sequence's keys are 0; a caller's `out`
-    may be wider: columns >= max_k are left alone); stats fp32 [R, H, 2] = (m, l) of every row and head, base 2."""
-    _dev(q, k, cu_rows, cu_k, q_rows, out)
+    may be wider: columns >= max_k are left alone); stats fp32 [R, H, 2] = (m, l) of every row and head, base 2.
+    slopes fp32 [H]: ALiBi, the base-2 logit loses log2(e) * slopes[h] * |q_pos[r] - j| (j = the key's position in its sequence);
+    q_pos int32 [R]: the position of every selected row in its key sequence (None: 0; ignored without slopes);
+    k_rows int64 [total keys]: k is a table and key t (in cu_k's numbering) is its row k_rows[t] -- the bits of a call on
+    k[k_rows]."""
+    _dev(q, k, cu_rows, cu_k, q_rows, out, slopes, q_pos, k_rows)
     for t in (q, k):
         assert _is16(t.dtype) and t.dtype == q.dtype and t.dim() == 2 and t.stride(1) == 1
     assert cu_rows.dtype == torch.int32 and cu_k.dtype == torch.int32 and cu_rows.numel() == cu_k.numel()
@@ -555,23 +560,38 @@ def attn_probs(q: torch.Tensor, k: torch.Tensor, cu_rows: torch.Tensor, cu_k: to
     stats = torch.empty((R, n_heads, 2), dtype=torch.float32, device=q.device)
     if scale is None:
         scale = 1.0 / math.sqrt(head_dim)
-    tk = k.shape[0]
+    if slopes is not None:
+        assert slopes.dtype == torch.float32 and slopes.is_contiguous() and slopes.numel() == n_heads
+    if q_pos is not None:
+        assert q_pos.dtype == torch.int32 and q_pos.is_contiguous() and q_pos.numel() == R
+    if k_rows is not None:
+        assert k_rows.dtype == torch.int64 and k_rows.is_contiguous()
+    tk = k.shape[0] if k_rows is None else k_rows.numel()
+    # index loads per pass: the key row map (8 bytes per key) and, with a bias, the positions and the slopes
+    idx_bytes = 2.0 * ((8.0 * tk if k_rows is not None else 0.0) + (4.0 * R if slopes is not None and q_pos is not None else 0.0)
+                       + (4.0 * n_heads if slopes is not None else 0.0) + (8.0 * R if q_rows is not None else 0.0))
 
     def launch():
         if R == 0:
             return
-        check(_lib.load().vf_attn_probs(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), _ptr(q_rows), cu_rows.data_ptr(),
+        check(_lib.load().vf_attn_probs_v2(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), _ptr(q_rows), cu_rows.data_ptr(),
                                         cu_k.data_ptr(), cu_rows.numel() - 1, int(max_rows), int(max_k), n_heads, head_dim,
                                         float(scale), _dt(q.dtype), ATTN_Q_LOG2 if q_log2 else 0, int(bool(per_head)),
-                                        stats.data_ptr(), out.data_ptr(), out.stride(0), _stream()), "vf_attn_probs")
+                                           stats.data_ptr(), out.data_ptr(), out.stride(0), _ptr(slopes),
+                                           _ptr(q_pos), _ptr(k_rows), _stream()),
+              "vf_attn_probs_v2")
 
-    def flops():       # 2 passes x 2 * sum_seq(rows * len_k) * H * dh, evaluated after the timed replay
+    def flops():       # 2 passes x 2 * sum_seq(rows * len_k) * H * dh (+ 3 per biased logit), evaluated after the timed replay
         lr = (cu_rows[1:] - cu_rows[:-1]).double()
         lk = (cu_k[1:] - cu_k[:-1]).double()
-        return 4.0 * float((lr * lk).sum().item()) * D
-    # K is read once per pass; the selected queries twice; out and stats written once
-    _run(launch, lambda: ("attn_probs", flops, 2.0 * D * (2 * tk + 2 * R) + 4.0 * n_out * int(max_k) + 16.0 * R * n_heads,
-                          f"H={n_heads} dh={head_dim} max_rows={int(max_rows)} max_k={int(max_k)}" + (" per_head" if per_head else ""),
+        pairs = float((lr * lk).sum().item())
+        return 4.0 * pairs * D + (6.0 * pairs * n_heads if slopes is not None else 0.0)
+    # K is read once per pass (every key of every sequence, through the row map where there is one); the selected queries
+    # twice; out and stats written once; the index loads once per pass
+    _run(launch, lambda: ("attn_probs_alibi" if slopes is not None else "attn_probs", flops,
+                          2.0 * D * (2 * tk + 2 * R) + 4.0 * n_out * int(max_k) + 16.0 * R * n_heads + idx_bytes,
+                          f"H={n_heads} dh={head_dim} max_rows={int(max_rows)} max_k={int(max_k)}" + (" per_head" if per_head else "")
+                          + (" k_rows" if k_rows is not None else ""),
                           family or _SCOPE))
     return out, stats
 

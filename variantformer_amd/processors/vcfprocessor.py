@@ -136,7 +136,8 @@ class VCFProcessor:
         predictions = trainer.predict(model, dataloader, ckpt_path=checkpoint_path)
         return self.format_output(vcf_dataset.query_df, predictions)
 
-    def predict_with_attention(self, model, checkpoint_path, trainer, dataloader, vcf_dataset, layers=None, per_head=False):
+    def predict_with_attention(self, model, checkpoint_path, trainer, dataloader, vcf_dataset, layers=None, per_head=False,
+                               gene_body=False):
         """`predict`'s frame plus the gene -> cCRE attention maps of the same forwards (no reference counterpart: flash-attn
         returns no probabilities).  New columns, one entry per gene:
           cre_attention         fp32 [len(layers), tissues, cCREs] (per_head: [len(layers), tissues, heads, cCREs]) -- how much the
@@ -144,10 +145,18 @@ class VCFProcessor:
                                 layer layers[k]; tissues in the order of the query, cCREs in the order of cre_names;
           cre_attention_layers  the gene-layer indices (layers=None: all; negative: from the end);
           cre_names, cre_start, cre_end   the manifest rows of the windows, where the dataset can name them (cre_table).
+        gene_body=True adds
+          gene_attention        fp32 [len(layers), tissues, 1 + chunks] (per_head: [len(layers), tissues, heads, 1 + chunks]) -- the
+                                same registry tokens' self attention over their own sequence: column 0 the token itself, column
+                                1 + c gene-body chunk c;
+          gene_chunk_seq_start, gene_chunk_seq_end, gene_chunk_start, gene_chunk_end   where each chunk lies in the encoded
+                                consensus sequence and (SNPs only, else null) on the genome, where the dataset can say
+                                (gene_chunk_table).
         A plain loop over the loader (the maps are read back per batch)."""
         model.trainer = trainer
         model.eval()
-        predictions = [model.predict_step_with_attention(batch, i, layers=layers, per_head=per_head)
+        kw = {"gene_body": True} if gene_body else {}
+        predictions = [model.predict_step_with_attention(batch, i, layers=layers, per_head=per_head, **kw)
                        for i, batch in enumerate(dataloader)]
         try:       # as Trainer.predict: what the self-healing LayerNorm fold did during this pass
             from ..seq2gene.model_combined_modulator import ln_fold_state
@@ -165,6 +174,17 @@ class VCFProcessor:
                 assert len(t) == m.shape[-1], f"{g}: cre_table names {len(t)} windows, the map has {m.shape[-1]} columns"
             for col, src in (("cre_names", "cre_name"), ("cre_start", "start_cre"), ("cre_end", "end_cre")):
                 df[col] = pd.Series([t[src].tolist() for t in tables], index=df.index, dtype=object)
+        if gene_body:
+            gmaps = [m for p in predictions for m in p["gene_attention"]]
+            df["gene_attention"] = pd.Series(gmaps, index=df.index, dtype=object)
+            if hasattr(vcf_dataset, "gene_chunk_table"):
+                tables = [vcf_dataset.gene_chunk_table(g) for g in df["gene_id"]]
+                for g, t, m in zip(df["gene_id"], tables, gmaps):    # a row per map column behind the registry token's
+                    assert len(t) == m.shape[-1] - 1, f"{g}: gene_chunk_table has {len(t)} chunks, the map {m.shape[-1] - 1}"
+                for col, src in (("gene_chunk_seq_start", "seq_start"), ("gene_chunk_seq_end", "seq_end"),
+                                 ("gene_chunk_start", "start"), ("gene_chunk_end", "end")):
+                    df[col] = pd.Series([[None if pd.isna(v) else int(v) for v in t[src]] for t in tables], index=df.index,
+                                        dtype=object)
         return df
 
     def predict_distributed(self, model, checkpoint_path, trainer, vcf_dataset, batch_size: int | None = None, costs=None,

@@ -803,8 +803,12 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
         if cap is not None:
             # the maps' rows are the registry-token rows -- the only rows the expression head reads; pb.registry_rows already
             # indexes the buffer the gene layers' cross attention projects its queries from (the gene stream itself)
-            self._attention_maps_supported()
-            cap.begin(pb.registry_rows, pb.cu_registry_cross, pb.max_tissues, pb.cu_cre, pb.max_cre)
+            self._attention_maps_supported(vep_ok=True)
+            # the same rows are position 0 of the gene stream's self-attention sequences (registry token + chunks): one row per
+            # sequence, the grouping the last layer's registry-rows form already uses
+            cap.begin(pb.registry_rows, pb.cu_registry_cross, pb.max_tissues, pb.cu_cre, pb.max_cre,
+                      gene_self=(pb.cu_registry, pb.cu_gene_self, pb.max_gene),
+                      shape=([len(t) for t in pb.tissues], list(pb.n_cre), list(pb.n_chunk)))
         if self._general:
             return self._forward_general(pb, cre_x, gene_x, return_cre)
         # registry token per (gene, tissue) + that gene's chunk rows (:357-366, layers.py:508-521)
@@ -947,10 +951,13 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
         with torch.no_grad():
             return self.predict_finish(self.predict_launch(self.prepare_batch(batch)), batch_idx, dataloader_idx)
 
-    def _attention_maps_supported(self) -> None:
-        """Raises NotImplementedError naming the option that has no attention-map capture."""
-        if self.vep:
-            raise NotImplementedError("attention maps: vep models (the ref / het / hom path) are not supported")
+    def _attention_maps_supported(self, vep_ok: bool = False) -> None:
+        """Raises NotImplementedError naming the option that has no attention-map capture.  vep_ok: the caller handles a vep
+        model (the forward itself, and variant_prediction_with_attention); predict_step_with_attention does not: it returns
+        predict_step's dict."""
+        if self.vep and not vep_ok:
+            raise NotImplementedError("attention maps: vep models (the ref / het / hom path) are not supported by "
+                                      "predict_step_with_attention; variant_prediction_with_attention returns their maps")
         off = [name for name, on in (("only_cross_attention", self.only_cross_attention), ("use_res", self.use_res),
                                      ("cross_alibi", self.cross_alibi), ("add_context_to_cres", self.add_context_to_cres),
                                      (f"gene_pooling={self.gene_pooling!r}", self.gene_pooling != "multi_registry")) if on]
@@ -958,32 +965,60 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
             raise NotImplementedError("attention maps: not supported with " + ", ".join(off) + " (the per-(gene, tissue) "
                                       "evaluation order of the options the shipped configuration leaves off)")
 
-    def predict_step_with_attention(self, batch, batch_idx, dataloader_idx=None, layers=None, per_head=False):
-        """predict_step's dict plus the gene -> cCRE attention maps of the same forward:
+    def predict_step_with_attention(self, batch, batch_idx, dataloader_idx=None, layers=None, per_head=False, gene_body=False):
+        """predict_step's dict plus the attention maps of the registry tokens in the same forward:
           "cre_attention"         per gene, fp32 numpy [len(layers), T_i, N_i] -- the head mean of the softmax of gene layer
                                   `layers[k]`'s cross attention on the registry-token row of tissue t (tissues in the order of
                                   tissue_context[i], cCREs in the order of cre_sequences[i]) -- or [len(layers), T_i, H, N_i]
                                   with per_head;
-          "cre_attention_layers"  the captured gene-layer indices.
+          "cre_attention_layers"  the captured gene-layer indices;
+          "gene_attention"        with gene_body: per gene, fp32 numpy [len(layers), T_i, 1 + C_i] ([len(layers), T_i, H, 1 + C_i]
+                                  with per_head) -- the same rows' SELF attention (ALiBi, the token at position 0): column 0 is
+                                  the registry token itself, column 1 + c gene-body chunk c in the order of gene_embeddings[i].
         layers: distinct gene-layer indices (negative: from the end; None: all; ValueError for an index out of range, an empty
         list or a layer named twice).  When the batch trips the LayerNorm-fold alert the
-        recomputation runs under the capture too and the maps are its maps."""
+        recomputation runs under the capture too and the maps are its maps.  A vep model has
+        variant_prediction_with_attention instead (variant_prediction's dict plus the same maps)."""
         self.eval()
         self._attention_maps_supported()
         sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
-        with torch.no_grad(), attn_maps.capture(sel, per_head) as cap:
-            pb = self.prepare_batch(batch)
-            out = self.predict_finish(self.predict_launch(pb), batch_idx, dataloader_idx)
-            maps = cap.maps.detach().cpu().numpy()                # the recomputation's when predict_finish healed the batch
-        H, per_gene, r = self.combined_modulator.num_heads, [], 0
-        for i in range(pb.n_genes):
-            t, nc = len(pb.tissues[i]), pb.n_cre[i]
-            if per_head:
-                per_gene.append(np.ascontiguousarray(maps[:, r * H:(r + t) * H, :nc].reshape(len(sel), t, H, nc)))
-            else:
-                per_gene.append(np.ascontiguousarray(maps[:, r:r + t, :nc]))
-            r += t
-        out["cre_attention"], out["cre_attention_layers"] = per_gene, sel
+        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body) as cap:
+            out = self.predict_finish(self.predict_launch(self.prepare_batch(batch)), batch_idx, dataloader_idx)
+            return self._with_attention(out, cap)         # the recomputation's maps when predict_finish healed the batch
+
+    def variant_prediction_with_attention(self, batch, layers=None, per_head=False, gene_body=False):
+        """variant_prediction's dict (bit for bit) plus "cre_attention", "cre_attention_layers" and, with gene_body,
+        "gene_attention" as predict_step_with_attention describes them, with one entry per genotype of the batch, in batch
+        order: ref, het, hom -- how a variant moved the model's attention.  The VEP forward keeps the full last gene layer (it
+        reads token-position rows of it), so every layer records through the row map of the registry rows.  When the batch
+        trips the LayerNorm-fold alert the recomputation runs under the capture too and the maps are its maps."""
+        self.eval()
+        self._attention_maps_supported(vep_ok=True)
+        sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
+        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body) as cap:
+            return self._with_attention(self.variant_prediction(batch), cap)
+
+    def _with_attention(self, out: dict, cap) -> dict:
+        """`out` plus the maps of the capture's most recent forward (call inside the capture block), split per gene."""
+        sel, per_head = list(cap.layers), cap.per_head
+        H = self.combined_modulator.num_heads
+
+        def per_gene(m, widths):
+            if m is None:                                 # no forward ran: an empty batch
+                return []
+            m = m.detach().cpu().numpy()
+            res, r = [], 0
+            for t, w in zip(cap.shape[0], widths):
+                if per_head:
+                    res.append(np.ascontiguousarray(m[:, r * H:(r + t) * H, :w].reshape(len(sel), t, H, w)))
+                else:
+                    res.append(np.ascontiguousarray(m[:, r:r + t, :w]))
+                r += t
+            return res
+        out["cre_attention"] = per_gene(cap.maps, cap.shape[1] if cap.shape else [])
+        out["cre_attention_layers"] = sel
+        if cap.gene_body:
+            out["gene_attention"] = per_gene(cap.gene_maps, [1 + c for c in cap.shape[2]] if cap.shape else [])
         return out
 
     def predict_launch(self, pb: PreparedBatch) -> PredictHandle:

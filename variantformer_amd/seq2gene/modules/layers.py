@@ -344,7 +344,7 @@ class MHA(nn.Module):
             if cap is not None:
                 if self.alibi_slopes is not None:
                     raise NotImplementedError("attention maps: cross_alibi (a positional bias in the gene -> cCRE cross "
-                                              "attention) has no probabilities kernel")
+                                              "attention) runs in the per-(gene, tissue) evaluation order, which is not captured")
                 cap.record(q, kv_bf16[:, :D], self.num_heads, self.head_dim, family=self.family)
             return ops.attn_varlen(q, kv_bf16[:, :D], kv_bf16[:, D:], cu_q, cu_k, max_q, max_k,
                                    self.num_heads, self.head_dim, self.alibi_slopes, family=self.family, q_log2=True)
@@ -417,6 +417,10 @@ class MHA(nn.Module):
         if rows is not None and not (runtime.switches().rows_in_attention and ops.attn_rows_supported(
                 self.head_dim, self.alibi_slopes is not None, cu_q.numel() - 1, self.num_heads, max_q, max_q, True)):
             qkv, rows = ops.gather_rows_bf16(qkv, rows), None
+        cap = attn_maps.running_self()     # a requested gene layer's self attention under capture(gene_body=True): its P, in fp32
+        if cap is not None:
+            cap.record_self(qkv[:, :D], qkv[:, D:2 * D], self.num_heads, self.head_dim, self.alibi_slopes, rows=rows,
+                            family=self.family)
         return ops.attn_varlen(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], cu_q, None, max_q, max_q,
                                self.num_heads, self.head_dim, self.alibi_slopes, family=self.family,
                                q_log2=True, rows=rows)
@@ -636,6 +640,9 @@ class ContextFlashAttentionEncoderLayer(nn.Module):
         kv = mha.project_qkv(h, self.norm1, out_rows=slice(D, None))               # [tokens, 2D]: all rows (K/V need them)
         hr = ops.ln_stream_rows(h, rows) if folded else ops.gather_rows_bf16(h, rows)
         q = mha.project_qkv(hr, self.norm1, out_rows=slice(0, D))                  # [R, D]
+        cap = attn_maps.running_self()
+        if cap is not None:                                                        # q already is the registry rows (compact)
+            cap.record_self(q, kv[:, :D], mha.num_heads, mha.head_dim, mha.alibi_slopes, family=mha.family + "_registry_rows")
         a = ops.attn_varlen(q, kv[:, :D], kv[:, D:], cu_rows, cu_src, 1, max_src, mha.num_heads, mha.head_dim,
                             mha.alibi_slopes, q_at_start=True, family=mha.family + "_registry_rows",
                             q_log2=True)

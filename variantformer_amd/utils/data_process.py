@@ -302,13 +302,20 @@ class ExtractSeqFromBed:
         return df
 
     # -- gene body -------------------------------------------------------------------------------------
-    def apply_bcftools_consensus_to_gene(self, chrom, strand, start, end, vcf_file, variant_type: str = None):
+    def gene_region(self, strand, start, end):
+        """The 0-based half-open reference interval a gene body's consensus is built from (before clipping at the
+        chromosome end): ONE statement of it, for the builder below and for callers that map the sequence back to the genome
+        (VCFDataset.gene_chunk_table)."""
         if strand == "-":
             start = max(int(start), int(end) - self.neighbour_hood)
             end = int(end) + self.upstream_neighbour_hood
         else:
             start = max(0, int(start) - self.upstream_neighbour_hood)
             end = min(int(end), int(start) + self.neighbour_hood)     # NB: `start` is already shifted (reference :396-401)
+        return start, end
+
+    def apply_bcftools_consensus_to_gene(self, chrom, strand, start, end, vcf_file, variant_type: str = None):
+        start, end = self.gene_region(strand, start, end)
         seq, _ = self._consensus(chrom, start, end, vcf_file, variant_type)
         if seq is None:
             raise ValueError(f"Error extracting {chrom}:{start + 1}-{end}")

@@ -67,22 +67,26 @@ class BPEEncoder:
             raise _lib.VFError("vf_bpe_encode failed")
         return ids[:n].copy(), starts[:n].copy()
 
-    def encode_forward(self, seq: str, max_tokens: int | None = None) -> np.ndarray:
+    def encode_forward(self, seq: str, max_tokens: int | None = None, with_starts: bool = False):
         """Token ids of one strand, int32.  Same ids as encode([seq, "A"])[0]: the C++ encoder upper-cases and
         splits at invalid characters itself, so the Python-side normalize() pass and the token strings are skipped
         (the sample builders need neither).  max_tokens: only the first max_tokens tokens -- exactly those of the full
-        encoding (vf_bpe_encode_prefix), at the cost of encoding ~5 characters per requested token instead of all of `seq`."""
+        encoding (vf_bpe_encode_prefix), at the cost of encoding ~5 characters per requested token instead of all of `seq`.
+        with_starts: (ids, start offset of every token in `seq`, int64) instead of the ids alone."""
         if max_tokens is None:
-            return self.encode_ids(seq)[0]
+            ids, starts = self.encode_ids(seq)
+            return (ids, starts) if with_starts else ids
         if self._h is None:
             self.load_vocabulary()
         raw = seq.encode("ascii", errors="replace")
         cap = min(len(raw), int(max_tokens)) + 1
         ids = np.empty(cap, dtype=np.int32)
-        n = self._lib.vf_bpe_encode_prefix(self._h, raw, len(raw), int(max_tokens), ids.ctypes.data, None, cap)
+        starts = np.empty(cap, dtype=np.int64) if with_starts else None
+        n = self._lib.vf_bpe_encode_prefix(self._h, raw, len(raw), int(max_tokens), ids.ctypes.data,
+                                           None if starts is None else starts.ctypes.data, cap)
         if n < 0:
             raise _lib.VFError("vf_bpe_encode_prefix failed")
-        return ids[:n].copy()
+        return (ids[:n].copy(), starts[:n].copy()) if with_starts else ids[:n].copy()
 
     # -- reference interface ------------------------------------------------------------------------
     def normalize(self, sequences):
