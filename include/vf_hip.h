@@ -60,7 +60,9 @@ const char* vf_last_kernel(int which);
  * (layers.py:78-80,159-162; seq2reg/modules.py:145-147,184-187), cre_map/gene_map
  * (seq2gene/model_combined_modulator.py:502-507,610-612), TissueExpressionHeads Linear layers
  * (layers.py:1078-1087).  Requires K % 8 == 0, N % 8 == 0 (N % 32 == 0 for GEGLU); fast MFMA
- * path when K % 64 == 0.
+ * path when K % 64 == 0.  Row offsets are 64-bit (M x ld* may pass 2^31 elements and 2^32 bytes).  The generic path
+ * (K % 64 != 0) puts ceil(M / 64) blocks on grid.y: M beyond 64 x the device's hipDeviceAttributeMaxGridDimY (~4.2 million
+ * rows) is refused (VF_ERR_INVALID_ARG) before anything is launched.
  * Non-finite operands (every vf_gemm* entry): a NaN in A makes its output row NaN, one in a W row or in bias[n] its
  * output column, one in the residual that element -- every other element keeps the bits of the call without it; 16-bit outputs
  * are rounded to nearest even, fp16 values beyond 65504 become +-Inf and fp16 subnormals are kept, as torch's cast does. */
@@ -154,6 +156,10 @@ int vf_pack_geglu_rows(const void* W, const float* bias, void* W_out, float* bia
  * accumulation.  dh in {32, 48, 64, 96, 128} (every multiple of 8 up to 256: vf_attn_varlen_fwd_v3).  cu_seqlens_*: int32 [n_seq+1] device arrays.
  * alibi_slopes: fp32 [H] device array or NULL.  Sequences with 0 queries are skipped; the rows of
  * queries whose key sequence is empty are written as zeros (flash-attn's convention).
+ * Sizes (every vf_attn_varlen_fwd* entry): token offsets are 64-bit (token x stride may pass 2^31 elements and 2^32 bytes, any
+ * q_stride / o_stride), but the offset of a key INSIDE its sequence is formed with a 24-bit multiply: max_seqlen_k, k_stride
+ * and v_stride must each stay below 2^24 and max_seqlen_k * max(k_stride, v_stride) below 2^31 elements; anything beyond is
+ * refused (VF_ERR_INVALID_ARG, the limit named in vf_last_error()) before anything is launched.
  * Non-finite operands (every vf_attn_* entry): a NaN in K makes every output of its (sequence, head) NaN, one in V
  * its column there, one in a query row that row of the head; every other sequence, head, column and row keeps the bits of the
  * call without it.  An Inf in V gives a non-finite column (a one-key sequence returns its V row exactly, +-Inf included). */
@@ -241,7 +247,8 @@ int vf_attn_varlen_fwd_rows(const void* q, const void* k, const void* v, void* o
  * log(count) added to the logit.  q [tokens, >= H*dh] 16-bit, pre-scaled by softmax_scale * log2 e (VF_ATTN_Q_LOG2 form);
  * kv_table [C, >= 2*H*dh] 16-bit = (K | V) of the C <= 16 distinct rows, heads packed (head, dh); log2_count fp32 [n_seq, C] =
  * log2 of how often row c occurs among sequence s's keys (-inf: not at all; every sequence holds >= 1 key);
- * out [tokens, >= H*dh] 16-bit.  fp32 scores, fp32-normalised weights, one rounding of the output.  A row with log2_count = -inf
+ * out [tokens, >= H*dh] 16-bit.  fp32 scores, fp32-normalised weights, one rounding of the output.  n_seq <= 65 535 (the sequences
+ * sit on grid.y; more is refused before anything is launched).  A row with log2_count = -inf
  * is not among the sequence's keys: nothing in it, a NaN included, reaches that sequence's outputs. */
 int vf_attn_counted_keys(const void* q, int64_t q_stride, const void* kv_table, int64_t kv_stride, const float* log2_count,
                          const int32_t* cu_seqlens_q, int n_seq, int max_seqlen_q, int C, int H, int dh,
@@ -266,7 +273,8 @@ int vf_attn_counted_keys(const void* q, int64_t q_stride, const void* kv_table, 
  * Non-finite operands: a NaN in a K row of (sequence, head) makes that head's probabilities of that sequence's
  * rows NaN (and so their head mean), one in a query row that row; every other row keeps the bits of the call without it.
  * dh in {32, 48, 64, 96, 128}; any other dh, a null pointer (q_rows alone may be NULL), n_seq < 0, max_rows < 0,
- * ldo < max_seqlen_k, a stride < H * dh or a bad dtype is refused before anything is launched; so are q / k that are not
+ * ldo < max_seqlen_k, a stride < H * dh, a bad dtype, n_seq > 65 535 or max_rows > 64 * 65 535 (the sequences sit on grid.z,
+ * the row tiles on grid.y) is refused before anything is launched; so are q / k that are not
  * 16-byte aligned or whose row strides are not multiples of 8 elements (the fragments are 16-byte loads, as in
  * vf_attn_varlen_fwd), and stats / out that are not 4-byte aligned.  n_seq == 0 or max_rows == 0 (no selected rows) is VF_OK
  * with nothing launched.  vf_last_kernel(1) names the kernel afterwards. */
@@ -307,7 +315,7 @@ int vf_attn_probs_v2(const void* q, int64_t q_stride, const void* k, int64_t k_s
  * [H * Cp, D] matrix built once per weights -- and out_proj(sum_c w_c v_c) is w . (Wo_h v_c), a GEMM with K = H * Cp (Cp >= C,
  * even, H * Cp % 64 == 0 for the GEMM; padding slots are zero).  Between the two GEMMs:
  *   out[t, h * Cp + c] = 16-bit( softmax_c( scores[t, h * Cp + c] + log2_count[seq(t), c] ) ),  0 for c >= C.
- * scores fp32 [tokens, lds >= H * Cp] base-2 logits; out 16-bit [tokens, ldo >= H * Cp].  Replaces, for the CRE layers, Wq + the
+ * scores fp32 [tokens, lds >= H * Cp] base-2 logits; out 16-bit [tokens, ldo >= H * Cp].  n_seq <= 65 535 (grid.y; refused beyond).  Replaces, for the CRE layers, Wq + the
  * flash-attn cross forward + the K = D half of out_proj (seq2gene/modules/layers.py:421-439, 156-158). */
 int vf_softmax_counted(const float* scores, int64_t lds, const float* log2_count, const int32_t* cu_seqlens_q, int n_seq,
                        int max_seqlen_q, int H, int Cp, int C, void* out, int64_t ldo, int out_dtype, void* stream);

@@ -7,18 +7,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.attn_probs_alibi_cases import GEOMETRIES, SENTINEL, AlibiCase, _cu, rows_with_keys
+from tests.attn_probs_alibi_cases import GEOMETRIES, P_TOL, SENTINEL, AlibiCase, _cu, rows_with_keys
+from tests.attn_probs_alibi_cases import prob_err as _err              # (the limit and its measurement are stated there)
 
 pytestmark = pytest.mark.gpu
-
-# max |P - P64| / rowmax(P64).  MEASURED: the largest value on MI355X over the whole parametrisation of
-# test_alibi_probs_against_float64 (1.080e-06, at H = 8, dh = 64, fp16 operands, scale applied by the kernel; the bias-free
-# entry's figure is 6.9e-7: the biased logits reach magnitude ~360, where one fp32 ulp is 3e-5, but the keys that carry a row's
-# weight are those whose biased logit is near the row maximum, and the error is taken relative to that maximum).  The limit is
-# 4 x that (another compiler's fp32 summation order), and never above 1e-4: beyond it the arithmetic is not fp32.
-MEASURED = 1.1e-6
-P_TOL = min(4 * MEASURED, 1e-4)
-assert P_TOL <= 1e-4
 
 
 @pytest.fixture(scope="module")
@@ -27,12 +19,6 @@ def ops():
         pytest.skip("needs a GPU")
     from variantformer_amd import ops as _ops
     return _ops
-
-
-def _err(P, P64):
-    rowmax = P64.max(dim=-1, keepdim=True).values
-    ok = rowmax[..., 0] > 0
-    return float(((P.double() - P64).abs() / rowmax.clamp_min(1e-300))[ok].max())
 
 
 def _check_layout(case, out, P64, per_head):

@@ -112,3 +112,73 @@ def test_create_refuses_merge_lists_the_bucket_order_cannot_serve():
     # an operand that is created only later
     bad2 = np.array([[4, 0, 5], [0, 1, 4]], np.int32)
     assert not lib.vf_bpe_create(char_ids.ctypes.data, 7, bad2.ctypes.data, len(bad2))
+
+
+def _prefix_texts(rng, n):
+    """Texts of n characters: random ACGT, repetitive ones, N runs, mixed case, 5 % other IUPAC codes."""
+    acgt = "".join(rng.choice(list("ACGT"), n)) if n else ""
+    out = [("acgt", acgt)]
+    for unit in ("A", "AC", "AAT", "GGGCGG"):
+        out.append((f"rep_{unit}", (unit * (n // len(unit) + 1))[:n]))
+    with_n = list(acgt)
+    for a in rng.integers(0, max(n, 1), 1 + n // 500):
+        for j in range(int(a), min(n, int(a) + int(rng.integers(1, 40)))):
+            with_n[j] = "N"
+    out.append(("n_runs", "".join(with_n)))
+    out.append(("mixed_case", "".join(c.lower() if f else c for c, f in zip(acgt, rng.random(n) < 0.5))))
+    out.append(("lower", acgt.lower()))
+    iupac = rng.choice(list("ACGTRYSWKMBDHV"), n, p=[.2375] * 4 + [.005] * 10) if n else []
+    out.append(("iupac", "".join(iupac)))
+    return out
+
+
+def _truncated_vocab(tmp_path, n_merges):
+    """The shipped tokenizer JSON cut down to its first n_merges merges -> (path, margin of vf_bpe_encode_prefix)."""
+    from variantformer_amd.utils.seq import DEFAULT_VOCAB
+    with open(DEFAULT_VOCAB) as f:
+        spec = json.load(f)
+    merges = spec["model"]["merges"][:n_merges]
+    pairs = [m.split(" ") if isinstance(m, str) else m for m in merges]
+    keep = {a + b for a, b in pairs}
+    spec["model"]["merges"] = merges
+    spec["model"]["vocab"] = {t: i for t, i in spec["model"]["vocab"].items() if len(t) == 1 or t in keep}
+    path = tmp_path / f"bpe_first_{n_merges}.json"
+    path.write_text(json.dumps(spec))
+    return str(path), len(merges) * max(len(a + b) for a, b in pairs)
+
+
+@pytest.mark.parametrize("n_merges", [None, 8, 40], ids=["shipped", "first8", "first40"])
+def test_encode_forward_prefix_equals_full_encoding(n_merges, tmp_path):
+    """enc.encode_forward(s, max_tokens=m, with_starts=True) == (ids[:m], starts[:m]) of enc.encode_ids(s): the sample
+    builder's prefix encoder (vf_bpe_encode_prefix) against the full encoding, for random, repetitive, N-split, mixed-case
+    and IUPAC texts of 0 ... 60 000 characters and m from 0 to beyond the token count.  The shipped vocabulary's margin
+    (ranks x longest token) is thousands of characters, so only the longest texts are really cut there; the same property
+    on the first 8 and the first 40 merges (margins of tens of characters) sends short texts down the cut path too.  A
+    word is cut when it is longer than 2 * margin + 4 * m: the test counts such cases instead of instrumenting the code."""
+    import numpy as np
+    from variantformer_amd.utils.seq import DEFAULT_VOCAB, BPEEncoder
+    enc = BPEEncoder()
+    if n_merges is None:
+        with open(DEFAULT_VOCAB) as f:
+            pairs = [m.split(" ") if isinstance(m, str) else m for m in json.load(f)["model"]["merges"]]
+        enc.load_vocabulary()
+        margin = len(pairs) * max(len(a + b) for a, b in pairs)
+    else:
+        path, margin = _truncated_vocab(tmp_path, n_merges)
+        enc.load_vocabulary(path)
+    rng = np.random.default_rng(2024)
+    n_cases = n_cut = 0
+    for n in (0, 1, 5, 300, 3000, 20000, 60000):
+        for kind, s in _prefix_texts(rng, n):
+            assert len(s) == n
+            ids, starts = enc.encode_ids(s)
+            for m in sorted({0, 1, 2, 7, 100, 1000, n // 3, n // 2, max(n - 1, 0), n, n + 5}):
+                got_ids, got_starts = enc.encode_forward(s, max_tokens=m, with_starts=True)
+                assert got_ids.tolist() == ids[:m].tolist(), (kind, n, m)
+                assert got_starts.tolist() == starts[:m].tolist(), (kind, n, m)
+                assert enc.encode_forward(s, max_tokens=m).tolist() == ids[:m].tolist(), (kind, n, m)
+                n_cases += 1
+                if kind == "acgt" or kind.startswith("rep_"):       # upper-case ACGT only: certainly ONE word, of length n
+                    n_cut += n > 2 * margin + 4 * m
+    assert n_cases >= 400
+    assert n_cut >= 1, f"no text was long enough to be cut (margin {margin})"

@@ -1431,7 +1431,9 @@ static int attn_dispatch(const void* q, const void* k, const void* v, void* out,
     if (n_seq == 0 || max_seqlen_q <= 0 || max_seqlen_k <= 0) return VF_OK;
     VF_REQUIRE(max_seqlen_k < (1 << 24) && k_stride < (1 << 24) && v_stride < (1 << 24) &&
                    (int64_t)max_seqlen_k * (k_stride > v_stride ? k_stride : v_stride) < (1LL << 31),
-               "vf_attn_varlen_fwd: max_seqlen_k * row stride must stay below 2^31 elements");
+               "vf_attn_varlen_fwd: max_seqlen_k=%d, k_stride=%ld, v_stride=%ld: each must stay below 2^24 and max_seqlen_k * "
+               "row stride below 2^31 elements (the tiled kernels form the key offset with a 24-bit multiply)",
+               max_seqlen_k, (long)k_stride, (long)v_stride);
     AttnParamsPad P;
     P.q = (const unsigned short*)q; P.k = (const unsigned short*)k; P.v = (const unsigned short*)v;
     P.out = (unsigned short*)out;

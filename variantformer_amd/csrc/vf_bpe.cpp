@@ -207,7 +207,7 @@ extern "C" int64_t vf_bpe_encode(const void* h, const char* seq, int64_t len, in
 // hold the same symbols left of some frontier before a rank is processed, they hold the same symbols left of (frontier - 1 symbol)
 // after it: a difference on the right -- the text beyond a cut -- moves left by at most ONE symbol per rank, and a symbol never
 // exceeds the longest token.  Tokens that end at least  n_rank x max_token_len  characters before the cut are therefore those of
-// the full encoding (tests/test_bpe_cpu.py compares with the full encoding at every cut of random and repetitive texts).
+// the full encoding (tests/test_bpe_cpu.py::test_encode_forward_prefix_equals_full_encoding compares with the full encoding).
 extern "C" int64_t vf_bpe_encode_prefix(const void* h, const char* seq, int64_t len, int64_t max_tokens, int32_t* ids_out,
                                         int64_t* starts_out, int64_t capacity) {
     if (!h || (!seq && len > 0) || len < 0 || max_tokens < 0) return -1;

@@ -1591,6 +1591,25 @@ template <int EPI, int DT>
 int launch_gemm(const void* A, int64_t lda, const void* W, const float* bias, const float* res, int64_t ldr, void* out,
                 int64_t ldo, int M, int N, int K, int variant, hipStream_t st) {
     if (K % 64 != 0) {
+        // ceil(M / 64) row blocks sit on grid.y, which the device limits (65 535 or 65 536 blocks, M ~ 4.2 million rows):
+        // refused by name here instead of failing inside the launch
+        static int max_grid_y[VF_MAX_DEVICES] = {};
+        const int dev = vf_current_device();
+        int limit = 65535;
+        if (dev >= 0) {
+            if (max_grid_y[dev] == 0) {
+                int v = 0;
+                if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxGridDimY, dev) != hipSuccess || v <= 0) {
+                    (void)hipGetLastError();
+                    v = 65535;
+                }
+                max_grid_y[dev] = v;
+            }
+            limit = max_grid_y[dev];
+        }
+        VF_REQUIRE(((long)M + 63) / 64 <= limit,
+                   "vf_gemm: K=%d is not a multiple of 64, and the generic kernel puts ceil(M / 64) = %d row blocks on "
+                   "grid.y, above the device's limit of %d (hipDeviceAttributeMaxGridDimY): split M", K, (int)(((long)M + 63) / 64), limit);
         dim3 grid((N + 63) / 64, (M + 63) / 64);
         vf_note_kernel(0, "gemm_generic_kernel");
         hipLaunchKernelGGL((gemm_generic_kernel<EPI, DT>), grid, dim3(256), 0, st, (const unsigned short*)A, lda,
