@@ -65,7 +65,11 @@ const char* vf_last_kernel(int which);
  * rows) is refused (VF_ERR_INVALID_ARG) before anything is launched.
  * Non-finite operands (every vf_gemm* entry): a NaN in A makes its output row NaN, one in a W row or in bias[n] its
  * output column, one in the residual that element -- every other element keeps the bits of the call without it; 16-bit outputs
- * are rounded to nearest even, fp16 values beyond 65504 become +-Inf and fp16 subnormals are kept, as torch's cast does. */
+ * are rounded to nearest even, fp16 values beyond 65504 become +-Inf and fp16 subnormals are kept, as torch's cast does.
+ * Write set (every vf_gemm* entry): columns [0, N_out) of rows [0, M) of out (N_out = N / 2 for GEGLU) and nothing else -- the
+ * ldo - N_out elements between two rows are not touched -- and no byte outside the M x K of A, the N x K of W, bias[N] and the
+ * M x N of the residual reaches a result.  The same holds for out16 and t16_out; part_stats is written in full, every
+ * (part, row) pair, so vf_ln_finalize* may read all of it. */
 int vf_gemm_bf16(const void* A, int64_t lda, const void* W, const float* bias,
                  const float* residual, int64_t ldr, void* out, int64_t ldo,
                  int M, int N, int K, int epilogue, void* stream);
@@ -156,6 +160,9 @@ int vf_pack_geglu_rows(const void* W, const float* bias, void* W_out, float* bia
  * accumulation.  dh in {32, 48, 64, 96, 128} (every multiple of 8 up to 256: vf_attn_varlen_fwd_v3).  cu_seqlens_*: int32 [n_seq+1] device arrays.
  * alibi_slopes: fp32 [H] device array or NULL.  Sequences with 0 queries are skipped; the rows of
  * queries whose key sequence is empty are written as zeros (flash-attn's convention).
+ * Write set (every vf_attn_varlen_fwd* entry, vf_attn_counted_keys and vf_softmax_counted): the first H * dh (H * Cp) columns of
+ * the output rows of the tokens [0, cu_seqlens_q[n_seq]).  A buffer with more rows keeps what it held in the rows at or past
+ * cu_seqlens_q[n_seq], and columns at or past H * dh (H * Cp) of every row are not touched.
  * Sizes (every vf_attn_varlen_fwd* entry): token offsets are 64-bit (token x stride may pass 2^31 elements and 2^32 bytes, any
  * q_stride / o_stride), but the offset of a key INSIDE its sequence is formed with a 24-bit multiply: max_seqlen_k, k_stride
  * and v_stride must each stay below 2^24 and max_seqlen_k * max(k_stride, v_stride) below 2^31 elements; anything beyond is
