@@ -3,6 +3,9 @@ production depth): step time with the capture off, with the gene -> cCRE maps of
 layers, with BOTH maps (gene -> cCRE and gene body) of the last layer and of all layers, and the two probabilities kernels' own
 times and algorithmic bytes / time against the HBM peak (ops.KernelTimer).  One JSON line, also written to
 profiles/attn_maps_bench_gene_body.json (profiles/attn_maps_bench.json is the run before the gene-body maps existed).
+Then the cCRE CONTRIBUTION maps (capture(contributions=True): a second, per-head probabilities launch and vf_attn_contrib per
+captured layer): step time for the last layer and for all layers beside the capture-off step of the same run, and the
+contribution launches' own ops.KernelTimer time; a second JSON line, written to profiles/attn_contrib_bench.json.
 
     python scripts/attn_maps_bench.py [--steps 6] [--warmup 3] [--genes-per-step 32] [--layers N]
 
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--tissues", type=int, default=54)
     ap.add_argument("--layers", type=int, default=None, help="override modulator depth (debug only)")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "attn_maps_bench_gene_body.json"))
+    ap.add_argument("--contrib-out", default=os.path.join(REPO, "profiles", "attn_contrib_bench.json"))
     args = ap.parse_args()
 
     import bench
@@ -45,17 +49,19 @@ def main():
     batch = make_batch(20251205, [args.n_cre] * G, [args.n_chunks] * G, [tissues] * G, 200)
     n_layers = len(model.combined_modulator.gene_layers)
 
-    def timed(layers, d2h, gene_body=False):
+    def timed(layers, d2h, gene_body=False, contributions=False):
         def step():
             if layers is None:
                 model.forward_prepared(pb)[0].cpu()
                 return
-            with attn_maps.capture(layers, gene_body=gene_body) as cap:
+            with attn_maps.capture(layers, gene_body=gene_body, contributions=contributions) as cap:
                 model.forward_prepared(pb)[0].cpu()
                 if d2h:
                     cap.maps.cpu()
                     if gene_body:
                         cap.gene_maps.cpu()
+                    if contributions:
+                        cap.contrib.cpu()
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
@@ -81,6 +87,16 @@ def main():
         with attn_maps.capture(list(range(n_layers)), gene_body=True):
             model.forward_prepared(pb)[0].cpu()
         summ = ops.TIMER.summary()
+        ops.TIMER = None
+        con_last = timed([n_layers - 1], False, contributions=True)
+        con_last_d2h = timed([n_layers - 1], True, contributions=True)
+        con_every = timed(list(range(n_layers)), False, contributions=True)
+        con_every_d2h = timed(list(range(n_layers)), True, contributions=True)
+        off_third = timed(None, False)
+        ops.TIMER = ops.KernelTimer()
+        with attn_maps.capture(list(range(n_layers)), contributions=True):
+            model.forward_prepared(pb)[0].cpu()
+        csumm = ops.TIMER.summary()
         ops.TIMER = None
     k = summ["attn_probs"]
     gbs = k["bytes"] / (k["total_ms"] * 1e-3) / 1e9
@@ -116,6 +132,33 @@ def main():
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         f.write(line + "\n")
+    kc = csumm["attn_contrib"]
+    kp = next(v for name, v in csumm.items() if name.startswith("attn_probs:") and name.endswith("_contrib"))
+    off_mean = (off + off_again + off_third) / 3.0
+    contrib = {
+        "shape": result["shape"], "steps": args.steps, "warmup": args.warmup,
+        "capture_off_ms": [round(off, 3), round(off_again, 3), round(off_third, 3)],
+        "maps_last_layer_ms": round(last, 3), "maps_all_layers_ms": round(every, 3),
+        "contributions_last_layer_ms": round(con_last, 3), "contributions_last_layer_with_d2h_ms": round(con_last_d2h, 3),
+        "contributions_all_layers_ms": round(con_every, 3), "contributions_all_layers_with_d2h_ms": round(con_every_d2h, 3),
+        "contributions_all_layers_over_capture_off": round(con_every / off_mean, 4),
+        "kernel_contrib": {"launches": kc["launches"], "total_ms": round(kc["total_ms"], 3),
+                           "ms_per_layer": round(kc["total_ms"] / kc["launches"], 4), "flops": kc["flops"], "bytes": kc["bytes"],
+                           "tflops": round(kc["flops"] / (kc["total_ms"] * 1e-3) / 1e12, 2),
+                           "note": "vf_attn_contrib, both kernels (the keys' Gram matrices on the fp32 MFMA, then the norms), "
+                                   "bracketed by HIP events on the launch stream.  flops = the Gram stage's upper triangle of head "
+                                   "pairs, 2 (dh^2 + dh) per key and pair, plus 2 H^2 per (row, key)"},
+        "kernel_per_head_probs": {"launches": kp["launches"], "total_ms": round(kp["total_ms"], 3),
+                                  "ms_per_layer": round(kp["total_ms"] / kp["launches"], 4),
+                                  "note": "the second, per-head vf_attn_probs launch into the scratch (the head-mean map keeps "
+                                          "its own call and bits)"},
+        "source_sha": bench.source_sha(),
+    }
+    cline = json.dumps(contrib)
+    print(cline)
+    os.makedirs(os.path.dirname(args.contrib_out), exist_ok=True)
+    with open(args.contrib_out, "w") as f:
+        f.write(cline + "\n")
 
 
 if __name__ == "__main__":

@@ -10,10 +10,12 @@ without a capture), so a capture requested around one model's forward never reac
         model.forward_prepared(pb)            # or predict_launch / predict_finish
     cap.maps                                  # fp32 [len(layers), sum T (* H), max_cre], row r = row r of `emb`
     cap.gene_maps                             # gene_body=True: fp32 [len(layers), sum T (* H), max_gene], column 0 = the token itself
+    cap.contrib                               # contributions=True: shaped like cap.maps; || sum_h P_h Wo_h v_j ||, what the token RECEIVED
 
 Who calls what: the model's forward `begin`s the capture with the batch's selected rows (the registry-token rows, the
 only rows the expression head reads); modulator_forward_packed wraps every GENE layer in `cap.layer(i, ...)`; MHA.attend's
-cross branch asks `running()` and, inside a requested gene layer only, hands q and K to `record`; MHA.attend_qkv and the last
+cross branch asks `running()` and, inside a requested gene layer only, hands q and K (with contributions: also V and the
+module's Gram matrix of out_proj, MHA.contrib_gram) to `record`; MHA.attend_qkv and the last
 layer's forward_packed_rows hand the self attention's q and K to `record_self` at the same places.  The CRE layers run
 outside any `layer(...)` block and are never captured.  DESIGN.md section 5b.
 """
@@ -29,12 +31,15 @@ _CAP: contextvars.ContextVar = contextvars.ContextVar("vf_attn_capture", default
 
 
 class Capture:
-    def __init__(self, layers, per_head: bool = False, gene_body: bool = False):
+    def __init__(self, layers, per_head: bool = False, gene_body: bool = False, contributions: bool = False):
         self.layers = tuple(int(i) for i in layers)     # distinct gene-layer indices, in the order of the first axis of `maps`
         if not self.layers or len(set(self.layers)) != len(self.layers):
             raise ValueError(f"attention maps: a capture needs distinct gene layers, got {list(self.layers)}")
         self.per_head = bool(per_head)
         self.gene_body = bool(gene_body)
+        self.contributions = bool(contributions)
+        self.contrib = None       # contributions: fp32, shaped like `maps`: the value-weighted norms of the most recent forward
+        self._scratch = None      # contributions: (gram fp32 [keys, H, H], per-head P fp32 [R * H, max_k] | None), one per forward
         self.maps = None          # fp32 [len(layers), R or R * H, max_k] of the most recent forward
         self.gene_maps = None     # gene_body: fp32 [len(layers), R or R * H, max_gene] of the most recent forward
         self.shape = None         # the forward's (tissues, cCREs, chunks) per gene: how the rows and columns split (host lists)
@@ -54,13 +59,19 @@ class Capture:
         self.shape = shape
         self.maps = None
         self.gene_maps = None
+        self.contrib = None
+        self._scratch = None
 
     def layer(self, i: int, compact: bool = False):
         """with cap.layer(i): gene layer i is running.  compact: its cross attention's query buffer already is the selected rows,
         in order (the last layer's registry-rows form)."""
         return _Layer(self, i, compact)
 
-    def record(self, q, k, n_heads: int, head_dim: int, family: str = "") -> None:
+    def record(self, q, k, n_heads: int, head_dim: int, family: str = "", v=None, s_gram=None) -> None:
+        """The running gene layer's cross attention: q / k its 16-bit query and key operands.  With contributions also v, the
+        value operand the attention kernel reads, and s_gram, fp32 [H, H, dh, dh] of the layer's out_proj (MHA.contrib_gram):
+        the per-head P (the map itself with per_head, else a second call into a scratch; the head-mean map keeps its call and
+        bits) feeds ops.attn_contrib.  Scratch and the keys' Gram buffer are made once per forward and shared by the layers."""
         slot, compact = self._running
         q_rows, cu_rows, max_rows, cu_k, max_k = self._rows
         n_out = self.n_rows * (n_heads if self.per_head else 1)
@@ -70,7 +81,20 @@ class Capture:
             assert q.shape[0] == self.n_rows
         ops.attn_probs(q, k, cu_rows, cu_k, max_rows, max_k, n_heads, head_dim, q_rows=None if compact else q_rows,
                        q_log2=True, per_head=self.per_head, out=self.maps[slot], family=family + "_maps")
-
+        if not self.contributions:
+            return
+        if self.contrib is None:
+            self.contrib = torch.empty((len(self.layers), n_out, max_k), dtype=torch.float32, device=q.device)
+            self._scratch = (torch.empty((k.shape[0], n_heads, n_heads), dtype=torch.float32, device=q.device),
+                             None if self.per_head else torch.empty((self.n_rows * n_heads, max_k), dtype=torch.float32, device=q.device))
+        gram, probs = self._scratch
+        if self.per_head:
+            probs = self.maps[slot]
+        else:
+            ops.attn_probs(q, k, cu_rows, cu_k, max_rows, max_k, n_heads, head_dim, q_rows=None if compact else q_rows,
+                           q_log2=True, per_head=True, out=probs, family=family + "_contrib")
+        ops.attn_contrib(v, s_gram, probs, cu_rows, cu_k, max_rows, max_k, n_heads, head_dim, gram=gram, out=self.contrib[slot],
+                         per_head=self.per_head, family=family + "_contrib")
 
     def record_self(self, q, k, n_heads: int, head_dim: int, slopes=None, rows=None, family: str = "") -> None:
         """The running gene layer's SELF attention: q / k its 16-bit query and key operands, slopes its ALiBi slopes (None: a
@@ -155,11 +179,12 @@ def running_self() -> Capture | None:
 
 
 class capture:
-    """with attn_maps.capture(layers, per_head, gene_body) as cap: every forward inside records the requested gene layers'
-    maps (gene_body: also those of the self attention over the gene body)."""
+    """with attn_maps.capture(layers, per_head, gene_body, contributions) as cap: every forward inside records the requested
+    gene layers' maps (gene_body: also those of the self attention over the gene body; contributions: also the value-weighted
+    norms of the cross attention, cap.contrib)."""
 
-    def __init__(self, layers, per_head: bool = False, gene_body: bool = False):
-        self.cap = Capture(layers, per_head, gene_body)
+    def __init__(self, layers, per_head: bool = False, gene_body: bool = False, contributions: bool = False):
+        self.cap = Capture(layers, per_head, gene_body, contributions)
 
     def __enter__(self) -> Capture:
         self.token = _CAP.set(self.cap)

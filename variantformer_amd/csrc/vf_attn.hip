@@ -2041,3 +2041,264 @@ extern "C" int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int
     return vf_attn_probs_v2(q, q_stride, k, k_stride, q_rows, cu_rows, cu_seqlens_k, n_seq, max_rows, max_seqlen_k, H, dh, scale,
                             operand_dtype, flags, per_head, stats, out, ldo, nullptr, nullptr, nullptr, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// vf_attn_contrib (include/vf_hip_next.h): the NORM of what key j hands to selected row r through out_proj,
+//   c[r, j] = sum_h P[r, h, j] * Wo[:, h*dh:(h+1)*dh] @ v[j, h, :],   n[r, j] = ||c[r, j]||_2,
+// without forming c.  With S[h, h'] = Wo_h^T Wo_h' (fp32 [H, H, dh, dh], per weights, the caller's):
+//   gram kernel   G[j, h, h'] = v[j, h, :]^T S[h, h'] v[j, h', :]     one block = one head pair h <= h' (S[h, h'] staged in LDS
+//                 once) walking a chunk of keys in 64-key tiles; a wave = 16 keys: T^T = S^T V_h^T on the exact fp32 MFMA
+//                 (16x16x4: rows e', columns keys, k = e in ascending order), then the dot with v[j, h', :] over the
+//                 accumulator registers and the four lane groups.  G[j, h', h] is the same number (S[h', h] = S[h, h']^T),
+//                 stored to both places.  Consecutive blocks are the pairs of ONE key chunk, so the chunk's value rows are
+//                 read from HBM once and from L2 by the other pairs.
+//   norm kernel   n[r, j]^2 = sum_h P[r, h, j] * (sum_h' G[j, h, h'] P[r, h', j]), h and h' ascending, fp32 fma; one block =
+//                 8 keys of one sequence (their G staged in LDS, zero padded to HT x HT) x all selected rows of the sequence.
+// fp32 throughout after the 16-bit loads of v; no atomics; every (row, key) is computed by one thread from row r's P, key j's
+// value row and S in a fixed order, so the bits depend neither on the rest of the call nor on max_rows / max_seqlen_k.  The
+// MFMA's columns (keys) are independent: a NaN in value row (j, h) reaches G[j, h, :] and G[j, :, h] alone.  Columns past a
+// sequence's keys are stored as 0, never multiplied; a negative radicand (rounding) becomes 0 through a comparison that a NaN
+// fails (contrib_sqrt), so a NaN stays a NaN.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct ContribParams {
+    const unsigned short* v;
+    int64_t v_stride;
+    const float* s_gram;
+    const float* probs;
+    int64_t ldp;
+    const int32_t* cu_rows;
+    const int32_t* cu_k;
+    int n_seq, H, max_k, per_head;
+    float* gram;
+    float* out;
+    int64_t ldo;
+};
+
+constexpr int GRAM_TILE = 64;       // keys per step of a block: 16 per wave
+constexpr int GRAM_CHUNK = 512;     // keys per block
+// LDS row strides in floats.  S rows: the four lane groups of an MFMA operand read rows 4s .. 4s + 3, 16 consecutive floats each:
+// a stride of 16 mod 32 puts them in four different quarters of the banks.  Value rows: 16 keys x 4 consecutive floats.
+template <int DH> constexpr int gram_ls() { return DH % 32 == 16 ? DH : DH + 16; }
+template <int DH> constexpr int gram_vs() { return DH + 4; }
+template <int DH> constexpr int gram_lds() { return 4 * (DH * gram_ls<DH>() + 2 * GRAM_TILE * gram_vs<DH>()); }
+
+template <int DT>
+__device__ __forceinline__ void gram_store8(float* dst, u32x4_t raw) {
+    f32x4_t lo, hi;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        lo[2 * i] = Op16<DT>::to_f32((unsigned short)(raw[i] & 0xffffu));
+        lo[2 * i + 1] = Op16<DT>::to_f32((unsigned short)(raw[i] >> 16));
+        hi[2 * i] = Op16<DT>::to_f32((unsigned short)(raw[2 + i] & 0xffffu));
+        hi[2 * i + 1] = Op16<DT>::to_f32((unsigned short)(raw[2 + i] >> 16));
+    }
+    *reinterpret_cast<f32x4_t*>(dst) = lo;
+    *reinterpret_cast<f32x4_t*>(dst + 4) = hi;
+}
+
+template <int DT, int DH>
+__global__ __launch_bounds__(256) void attn_contrib_gram_kernel(ContribParams P, int n_pairs) {
+    extern __shared__ __attribute__((aligned(16))) float gram_smem[];
+    constexpr int LS = gram_ls<DH>(), VS = gram_vs<DH>(), MT = DH / 16;
+    float* S = gram_smem;
+    float* Va = S + DH * LS;
+    float* Vb = Va + GRAM_TILE * VS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pair = (int)(blockIdx.x % (unsigned)n_pairs);
+    const int64_t key0 = (int64_t)(blockIdx.x / (unsigned)n_pairs) * GRAM_CHUNK;
+    const int64_t total = P.cu_k[P.n_seq];
+    if (key0 >= total) return;                                    // block-uniform
+    const int H = P.H;
+    int h = 0, rem = pair;                                        // the upper triangle, row by row
+    while (rem >= H - h) { rem -= H - h; ++h; }
+    const int h2 = h + rem;
+
+    const f32x4_t* sg = reinterpret_cast<const f32x4_t*>(P.s_gram + ((int64_t)h * H + h2) * DH * DH);
+    for (int c = tid; c < DH * DH / 4; c += 256)
+        *reinterpret_cast<f32x4_t*>(S + (c / (DH / 4)) * LS + 4 * (c % (DH / 4))) = sg[c];
+
+    const int kx = lane & 15, g = lane >> 4;
+    const int64_t key_end = key0 + GRAM_CHUNK < total ? key0 + GRAM_CHUNK : total;
+    for (int64_t t0 = key0; t0 < key_end; t0 += GRAM_TILE) {
+        __syncthreads();                                          // the previous tile's operands have been read
+        for (int c = tid; c < GRAM_TILE * DH / 8; c += 256) {
+            const int key = c / (DH / 8), part = c % (DH / 8);
+            u32x4_t ra = {0u, 0u, 0u, 0u}, rb = {0u, 0u, 0u, 0u};  // keys past the end: zeros, their results are not stored
+            if (t0 + key < total) {
+                const unsigned short* row = P.v + (t0 + key) * P.v_stride + 8 * part;
+                ra = *reinterpret_cast<const u32x4_t*>(row + h * DH);
+                rb = *reinterpret_cast<const u32x4_t*>(row + h2 * DH);
+            }
+            gram_store8<DT>(Va + key * VS + 8 * part, ra);
+            gram_store8<DT>(Vb + key * VS + 8 * part, rb);
+        }
+        __syncthreads();
+        const float* va = Va + (wave * 16 + kx) * VS + g;
+        const float* sr = S + g * LS + kx;
+        f32x4_t acc[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < DH / 4; ++s) {
+            const float b = va[4 * s];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(sr[4 * s * LS + 16 * mt], b, acc[mt], 0, 0, 0);
+        }
+        // lane (kx, g) holds T[key kx][e' = 16 mt + 4 g + reg]
+        const float* vb = Vb + (wave * 16 + kx) * VS + 4 * g;
+        float dot = 0.f;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const f32x4_t w = *reinterpret_cast<const f32x4_t*>(vb + 16 * mt);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dot = __builtin_fmaf(acc[mt][e], w[e], dot);
+        }
+        dot += __shfl_xor(dot, 16);
+        dot += __shfl_xor(dot, 32);
+        const int64_t kg = t0 + wave * 16 + kx;
+        if (g == 0 && kg < total) {
+            float* gp = P.gram + kg * H * H;
+            gp[h * H + h2] = dot;
+            gp[h2 * H + h] = dot;
+        }
+    }
+}
+
+// sqrt of a radicand that rounding may have pushed below zero: 0 there.  The comparison is made on the bits (negative, not -0,
+// not a NaN), so it holds whatever this file's -fno-honor-nans lets the compiler assume about a float comparison (an ordered
+// `x < 0` may become an unordered one, which a NaN passes; with the float form the NaN of a value row did not reach `out`):
+// a NaN is not negative and stays a NaN through the square root.
+__device__ __forceinline__ float contrib_sqrt(float x) {
+    const unsigned u = __float_as_uint(x);
+    return (u > 0x80000000u && u <= 0xff800000u) ? 0.f : __builtin_sqrtf(x);
+}
+
+template <int HT>
+__global__ __launch_bounds__(256) void attn_contrib_norm_kernel(ContribParams P) {
+    constexpr int KT = 8, GS = HT * HT + 4;
+    __shared__ __attribute__((aligned(16))) float G[KT * GS];
+    const int seq = blockIdx.y;
+    const int r0 = P.cu_rows[seq], n_rows = P.cu_rows[seq + 1] - r0;
+    if (n_rows <= 0) return;                                      // a sequence without selected rows writes nothing
+    const int k0 = P.cu_k[seq], len_k = P.cu_k[seq + 1] - k0;
+    const int kbase = blockIdx.x * KT;
+    const int tid = threadIdx.x, kx = tid & (KT - 1), slot = tid / KT;
+    const int j = kbase + kx, H = P.H;
+    if (kbase < len_k) {                                          // block-uniform; G of the tile's keys, zero padded to HT x HT
+        for (int c = tid; c < KT * HT * HT; c += 256) {
+            const int key = c / (HT * HT), a = (c / HT) % HT, b = c % HT;
+            float x = 0.f;
+            if (kbase + key < len_k && a < H && b < H) x = P.gram[(int64_t)(k0 + kbase + key) * H * H + a * H + b];
+            G[key * GS + a * HT + b] = x;
+        }
+        __syncthreads();
+    }
+    if (j >= P.max_k) return;
+    const float* gk = G + kx * GS;
+    for (int rr = slot; rr < n_rows; rr += 256 / KT) {
+        const int64_t r = r0 + rr;
+        if (j >= len_k) {                                         // past the sequence's keys: zeros
+            if (P.per_head) for (int h = 0; h < H; ++h) P.out[(r * H + h) * P.ldo + j] = 0.f;
+            else P.out[r * P.ldo + j] = 0.f;
+            continue;
+        }
+        float p[HT];
+#pragma unroll
+        for (int h = 0; h < HT; ++h) p[h] = h < H ? P.probs[(r * H + h) * P.ldp + j] : 0.f;
+        if (P.per_head) {
+#pragma unroll
+            for (int h = 0; h < HT; ++h)
+                if (h < H) {
+                    P.out[(r * H + h) * P.ldo + j] = p[h] * contrib_sqrt(gk[h * HT + h]);
+                }
+        } else {
+            float acc = 0.f;
+#pragma unroll
+            for (int h = 0; h < HT; ++h) {
+                float t = 0.f;
+#pragma unroll
+                for (int q = 0; q < HT / 4; ++q) {
+                    const f32x4_t w = *reinterpret_cast<const f32x4_t*>(gk + h * HT + 4 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) t = __builtin_fmaf(w[e], p[4 * q + e], t);
+                }
+                acc = __builtin_fmaf(p[h], t, acc);
+            }
+            P.out[r * P.ldo + j] = contrib_sqrt(acc);
+        }
+    }
+}
+
+template <int DT, int DH>
+static int launch_contrib_gram(const ContribParams& P, unsigned blocks, int n_pairs, hipStream_t st) {
+    auto kern = attn_contrib_gram_kernel<DT, DH>;
+    constexpr int lds = gram_lds<DH>();
+    if (lds > 65536) {                             // dh >= 96: above the default dynamic-LDS limit
+        static bool attr_set[VF_MAX_DEVICES] = {};
+        const int dev = vf_current_device();
+        if (dev < 0 || !attr_set[dev]) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
+                hipSuccess) {
+                (void)hipGetLastError();
+                vf_set_error("vf_attn_contrib: cannot reserve %d bytes of LDS", lds);
+                return VF_ERR_LAUNCH;
+            }
+            if (dev >= 0) attr_set[dev] = true;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, st, P, n_pairs);
+    VF_CHECK_LAUNCH("vf_attn_contrib");
+    return VF_OK;
+}
+
+template <int HT>
+static int launch_contrib_norm(const ContribParams& P, hipStream_t st) {
+    hipLaunchKernelGGL((attn_contrib_norm_kernel<HT>), dim3((P.max_k + 7) / 8, P.n_seq), dim3(256), 0, st, P);
+    VF_CHECK_LAUNCH("vf_attn_contrib");
+    return VF_OK;
+}
+
+}  // namespace
+
+extern "C" int vf_attn_contrib(const void* v, int64_t v_stride, const float* s_gram, const float* probs, int64_t ldp,
+                               const int32_t* cu_rows, const int32_t* cu_seqlens_k, int n_seq, int max_rows, int max_seqlen_k,
+                               int H, int dh, int operand_dtype, int per_head, float* gram, float* out, int64_t ldo, void* stream) {
+    const char* null_arg = !v ? "v" : !s_gram ? "s_gram" : !probs ? "probs" : !cu_rows ? "cu_rows" : !cu_seqlens_k ? "cu_seqlens_k"
+                           : !gram ? "gram" : !out ? "out" : nullptr;
+    VF_REQUIRE(!null_arg, "vf_attn_contrib: null pointer %s", null_arg);
+    VF_REQUIRE(operand_dtype == VF_BF16 || operand_dtype == VF_F16, "vf_attn_contrib: operand_dtype must be VF_BF16 or VF_F16");
+    VF_REQUIRE(legacy_dh(dh), "vf_attn_contrib: head_dim %d not supported (32/48/64/96/128)", dh);
+    VF_REQUIRE(H > 0 && H <= 32, "vf_attn_contrib: H=%d out of range (1 .. 32: the norm kernel holds a row's H probabilities in registers)", H);
+    VF_REQUIRE(n_seq >= 0 && max_rows >= 0 && max_seqlen_k >= 0,
+               "vf_attn_contrib: n_seq=%d max_rows=%d max_seqlen_k=%d out of range", n_seq, max_rows, max_seqlen_k);
+    VF_REQUIRE(ldo >= max_seqlen_k, "vf_attn_contrib: ldo=%ld is below max_seqlen_k=%d", (long)ldo, max_seqlen_k);
+    VF_REQUIRE(ldp >= max_seqlen_k, "vf_attn_contrib: ldp=%ld is below max_seqlen_k=%d", (long)ldp, max_seqlen_k);
+    VF_REQUIRE(v_stride >= (int64_t)H * dh, "vf_attn_contrib: v_stride=%ld must hold H * dh = %d elements", (long)v_stride, H * dh);
+    VF_REQUIRE(v_stride % 8 == 0 && ((uintptr_t)v % 16 == 0), "vf_attn_contrib: v rows must keep 16-byte alignment (v, v_stride)");
+    VF_REQUIRE(((uintptr_t)s_gram % 16 == 0) && ((uintptr_t)probs % 4 == 0) && ((uintptr_t)gram % 4 == 0) && ((uintptr_t)out % 4 == 0),
+               "vf_attn_contrib: s_gram must be 16-byte aligned, probs / gram / out 4-byte aligned");
+    if (n_seq == 0 || max_rows == 0) return VF_OK;
+    const int n_pairs = H * (H + 1) / 2;
+    const long chunks = ((long)n_seq * max_seqlen_k + GRAM_CHUNK - 1) / GRAM_CHUNK;
+    VF_REQUIRE(n_seq <= 65535 && (max_rows + 63) / 64 <= 65535 && chunks * n_pairs < (1L << 31),
+               "vf_attn_contrib: n_seq=%d max_rows=%d max_seqlen_k=%d exceed the grid limit", n_seq, max_rows, max_seqlen_k);
+    ContribParams P;
+    P.v = (const unsigned short*)v; P.v_stride = v_stride; P.s_gram = s_gram; P.probs = probs; P.ldp = ldp;
+    P.cu_rows = cu_rows; P.cu_k = cu_seqlens_k; P.n_seq = n_seq; P.H = H; P.max_k = max_seqlen_k; P.per_head = per_head ? 1 : 0;
+    P.gram = gram; P.out = out; P.ldo = ldo;
+    hipStream_t st = (hipStream_t)stream;
+    vf_note_kernel(1, "attn_contrib_kernel");
+    if (max_seqlen_k == 0) return VF_OK;
+    const unsigned blocks = (unsigned)(chunks * n_pairs);
+#define VF_CG(DT_) (dh == 32 ? launch_contrib_gram<DT_, 32>(P, blocks, n_pairs, st) : dh == 48 ? launch_contrib_gram<DT_, 48>(P, blocks, n_pairs, st) : \
+                    dh == 64 ? launch_contrib_gram<DT_, 64>(P, blocks, n_pairs, st) : dh == 96 ? launch_contrib_gram<DT_, 96>(P, blocks, n_pairs, st) : \
+                    launch_contrib_gram<DT_, 128>(P, blocks, n_pairs, st))
+    const int rc = operand_dtype == VF_BF16 ? VF_CG(VF_BF16) : VF_CG(VF_F16);
+#undef VF_CG
+    if (rc != VF_OK) return rc;
+    return H <= 4 ? launch_contrib_norm<4>(P, st) : H <= 8 ? launch_contrib_norm<8>(P, st)
+         : H <= 16 ? launch_contrib_norm<16>(P, st) : launch_contrib_norm<32>(P, st);
+}

@@ -596,6 +596,48 @@ def attn_probs(q: torch.Tensor, k: torch.Tensor, cu_rows: torch.Tensor, cu_k: to
     return out, stats
 
 
+def attn_contrib(v: torch.Tensor, s_gram: torch.Tensor, probs: torch.Tensor, cu_rows: torch.Tensor, cu_k: torch.Tensor,
+                 max_rows: int, max_k: int, n_heads: int, head_dim: int, gram: torch.Tensor, out: torch.Tensor,
+                 per_head: bool = False, family: str = ""):
+    """Value-weighted norms beside an attention map (vf_attn_contrib, include/vf_hip_next.h): out[r, j] = || sum_h P[r, h, j] *
+    Wo_h v[j, h] ||_2, or per head out[r * H + h, j] = P[r, h, j] * || Wo_h v[j, h] ||_2.  v [tk, >= H*dh] 16-bit row-strided view
+    (the value rows the attention kernel reads); s_gram fp32 [H, H, dh, dh] = Wo_h^T Wo_h' (per weights); probs fp32 [R * H, >=
+    max_k] = ops.attn_probs(per_head=True) of the same rows and grouping.  The caller owns every buffer, and nothing is made
+    here: gram fp32 [>= tk, H, H] (an output: the keys' Gram matrices) and out fp32 [R or R * H, >= max_k] are reused across
+    layers by the capture.  Columns past a sequence's keys are 0, columns >= max_k are left alone.  Returns out."""
+    _dev(v, s_gram, probs, cu_rows, cu_k, gram, out)
+    assert _is16(v.dtype) and v.dim() == 2 and v.stride(1) == 1
+    assert cu_rows.dtype == torch.int32 and cu_k.dtype == torch.int32 and cu_rows.numel() == cu_k.numel()
+    H, dh = int(n_heads), int(head_dim)
+    assert s_gram.dtype == torch.float32 and s_gram.is_contiguous() and tuple(s_gram.shape) == (H, H, dh, dh)
+    for t in (probs, out):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= max_k
+    assert probs.shape[0] % H == 0
+    R = probs.shape[0] // H
+    assert out.shape[0] == (R * H if per_head else R)
+    tk = v.shape[0]
+    assert gram.dtype == torch.float32 and gram.is_contiguous() and gram.numel() >= tk * H * H
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_attn_contrib(v.data_ptr(), v.stride(0), s_gram.data_ptr(), probs.data_ptr(), probs.stride(0),
+                                          cu_rows.data_ptr(), cu_k.data_ptr(), cu_rows.numel() - 1, int(max_rows), int(max_k), H, dh,
+                                          _dt(v.dtype), int(bool(per_head)), gram.data_ptr(), out.data_ptr(), out.stride(0),
+                                          _stream()), "vf_attn_contrib")
+
+    def flops():       # the Gram stage: every key x the upper triangle of head pairs x (dh^2 + dh) MACs; the norms: H^2 per (row, key)
+        lr = (cu_rows[1:] - cu_rows[:-1]).double()
+        lk = (cu_k[1:] - cu_k[:-1]).double()
+        return 2.0 * float(lk.sum().item()) * (H * (H + 1) / 2) * (dh * dh + dh) + 2.0 * float((lr * lk).sum().item()) * H * H
+    # v is read once per key chunk (the other head pairs of a chunk hit L2), S once, gram written and read once, P and out once
+    _run(launch, lambda: ("attn_contrib", flops,
+                          2.0 * tk * H * dh + 4.0 * s_gram.numel() + 8.0 * tk * H * H + 4.0 * R * H * int(max_k) + 4.0 * out.shape[0] * int(max_k),
+                          f"H={H} dh={dh} max_rows={int(max_rows)} max_k={int(max_k)}" + (" per_head" if per_head else ""),
+                          family or _SCOPE))
+    return out
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

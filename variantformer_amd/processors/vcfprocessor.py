@@ -137,7 +137,7 @@ class VCFProcessor:
         return self.format_output(vcf_dataset.query_df, predictions)
 
     def predict_with_attention(self, model, checkpoint_path, trainer, dataloader, vcf_dataset, layers=None, per_head=False,
-                               gene_body=False):
+                               gene_body=False, contributions=False):
         """`predict`'s frame plus the gene -> cCRE attention maps of the same forwards (no reference counterpart: flash-attn
         returns no probabilities).  New columns, one entry per gene:
           cre_attention         fp32 [len(layers), tissues, cCREs] (per_head: [len(layers), tissues, heads, cCREs]) -- how much the
@@ -152,10 +152,17 @@ class VCFProcessor:
           gene_chunk_seq_start, gene_chunk_seq_end, gene_chunk_start, gene_chunk_end   where each chunk lies in the encoded
                                 consensus sequence and (SNPs only, else null) on the genome, where the dataset can say
                                 (gene_chunk_table).
+        contributions=True adds
+          cre_contribution      fp32, shaped and ordered like cre_attention -- the norm of what each cCRE window adds to the
+                                registry token through the cross attention's output projection (value-weighted: a window with
+                                a large weight and a value near zero moves the token less than its weight suggests); the
+                                quantity to rank cCREs by.
         A plain loop over the loader (the maps are read back per batch)."""
         model.trainer = trainer
         model.eval()
         kw = {"gene_body": True} if gene_body else {}
+        if contributions:
+            kw["contributions"] = True
         predictions = [model.predict_step_with_attention(batch, i, layers=layers, per_head=per_head, **kw)
                        for i, batch in enumerate(dataloader)]
         try:       # as Trainer.predict: what the self-healing LayerNorm fold did during this pass
@@ -174,6 +181,8 @@ class VCFProcessor:
                 assert len(t) == m.shape[-1], f"{g}: cre_table names {len(t)} windows, the map has {m.shape[-1]} columns"
             for col, src in (("cre_names", "cre_name"), ("cre_start", "start_cre"), ("cre_end", "end_cre")):
                 df[col] = pd.Series([t[src].tolist() for t in tables], index=df.index, dtype=object)
+        if contributions:
+            df["cre_contribution"] = pd.Series([m for p in predictions for m in p["cre_contribution"]], index=df.index, dtype=object)
         if gene_body:
             gmaps = [m for p in predictions for m in p["gene_attention"]]
             df["gene_attention"] = pd.Series(gmaps, index=df.index, dtype=object)

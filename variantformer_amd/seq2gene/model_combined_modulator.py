@@ -965,7 +965,8 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
             raise NotImplementedError("attention maps: not supported with " + ", ".join(off) + " (the per-(gene, tissue) "
                                       "evaluation order of the options the shipped configuration leaves off)")
 
-    def predict_step_with_attention(self, batch, batch_idx, dataloader_idx=None, layers=None, per_head=False, gene_body=False):
+    def predict_step_with_attention(self, batch, batch_idx, dataloader_idx=None, layers=None, per_head=False, gene_body=False,
+                                    contributions=False):
         """predict_step's dict plus the attention maps of the registry tokens in the same forward:
           "cre_attention"         per gene, fp32 numpy [len(layers), T_i, N_i] -- the head mean of the softmax of gene layer
                                   `layers[k]`'s cross attention on the registry-token row of tissue t (tissues in the order of
@@ -975,6 +976,11 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
           "gene_attention"        with gene_body: per gene, fp32 numpy [len(layers), T_i, 1 + C_i] ([len(layers), T_i, H, 1 + C_i]
                                   with per_head) -- the same rows' SELF attention (ALiBi, the token at position 0): column 0 is
                                   the registry token itself, column 1 + c gene-body chunk c in the order of gene_embeddings[i].
+          "cre_contribution"      with contributions: per gene, fp32 numpy shaped like "cre_attention" -- the norm of the vector
+                                  that cCRE j adds to the registry token through the cross attention's out_proj,
+                                  || sum_h P[h, j] Wo_h v[j, h] || (per_head: P[h, j] || Wo_h v[j, h] ||, head h's own share):
+                                  what the token received, where "cre_attention" says where it looked.  Predictions and the
+                                  maps keep their bits with it.
         layers: distinct gene-layer indices (negative: from the end; None: all; ValueError for an index out of range, an empty
         list or a layer named twice).  When the batch trips the LayerNorm-fold alert the
         recomputation runs under the capture too and the maps are its maps.  A vep model has
@@ -982,20 +988,20 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
         self.eval()
         self._attention_maps_supported()
         sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
-        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body) as cap:
+        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions) as cap:
             out = self.predict_finish(self.predict_launch(self.prepare_batch(batch)), batch_idx, dataloader_idx)
             return self._with_attention(out, cap)         # the recomputation's maps when predict_finish healed the batch
 
-    def variant_prediction_with_attention(self, batch, layers=None, per_head=False, gene_body=False):
-        """variant_prediction's dict (bit for bit) plus "cre_attention", "cre_attention_layers" and, with gene_body,
-        "gene_attention" as predict_step_with_attention describes them, with one entry per genotype of the batch, in batch
-        order: ref, het, hom -- how a variant moved the model's attention.  The VEP forward keeps the full last gene layer (it
+    def variant_prediction_with_attention(self, batch, layers=None, per_head=False, gene_body=False, contributions=False):
+        """variant_prediction's dict (bit for bit) plus "cre_attention", "cre_attention_layers" and, with gene_body /
+        contributions, "gene_attention" / "cre_contribution" as predict_step_with_attention describes them, with one entry per
+        genotype of the batch, in batch order: ref, het, hom -- how a variant moved the model's attention.  The VEP forward keeps the full last gene layer (it
         reads token-position rows of it), so every layer records through the row map of the registry rows.  When the batch
         trips the LayerNorm-fold alert the recomputation runs under the capture too and the maps are its maps."""
         self.eval()
         self._attention_maps_supported(vep_ok=True)
         sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
-        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body) as cap:
+        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions) as cap:
             return self._with_attention(self.variant_prediction(batch), cap)
 
     def _with_attention(self, out: dict, cap) -> dict:
@@ -1019,6 +1025,8 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
         out["cre_attention_layers"] = sel
         if cap.gene_body:
             out["gene_attention"] = per_gene(cap.gene_maps, [1 + c for c in cap.shape[2]] if cap.shape else [])
+        if cap.contributions:
+            out["cre_contribution"] = per_gene(cap.contrib, cap.shape[1] if cap.shape else [])
         return out
 
     def predict_launch(self, pb: PreparedBatch) -> PredictHandle:

@@ -345,10 +345,25 @@ class MHA(nn.Module):
                 if self.alibi_slopes is not None:
                     raise NotImplementedError("attention maps: cross_alibi (a positional bias in the gene -> cCRE cross "
                                               "attention) runs in the per-(gene, tissue) evaluation order, which is not captured")
-                cap.record(q, kv_bf16[:, :D], self.num_heads, self.head_dim, family=self.family)
+                if cap.contributions:
+                    cap.record(q, kv_bf16[:, :D], self.num_heads, self.head_dim, family=self.family, v=kv_bf16[:, D:],
+                               s_gram=self.contrib_gram())
+                else:
+                    cap.record(q, kv_bf16[:, :D], self.num_heads, self.head_dim, family=self.family)
             return ops.attn_varlen(q, kv_bf16[:, :D], kv_bf16[:, D:], cu_q, cu_k, max_q, max_k,
                                    self.num_heads, self.head_dim, self.alibi_slopes, family=self.family, q_log2=True)
         return self.attend_qkv(self.project_qkv(x, norm), cu_q, max_q)
+
+    def contrib_gram(self) -> torch.Tensor:
+        """fp32 [H, H, dh, dh]: S[h, h', e, e'] = sum_d Wo[d, h*dh + e] * Wo[d, h'*dh + e'] of the 16-bit out_proj weight the model
+        multiplies (packed_linear), accumulated in float64 and rounded once: the per-weights operand of ops.attn_contrib
+        (contribution maps).  One-time weight preparation by torch, cached per (weights, operand type)."""
+        H, dh = self.num_heads, self.head_dim
+
+        def build():
+            w = packed_linear(self.out_proj)[0].double()                    # [D (out), D (in: head, dh)]
+            return (w.t() @ w).view(H, dh, H, dh).permute(0, 2, 1, 3).float().contiguous()
+        return weights.derived(self, "_vf_contrib_gram", (self.out_proj.weight,), build)
 
     def lowrank_tables(self, norm, table: torch.Tensor):
         """Weights of the LOW-RANK form of a cross attention whose keys / values are Wkv of the C rows of `table` (fp32 [C, D]):
