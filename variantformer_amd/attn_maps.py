@@ -11,12 +11,14 @@ without a capture), so a capture requested around one model's forward never reac
     cap.maps                                  # fp32 [len(layers), sum T (* H), max_cre], row r = row r of `emb`
     cap.gene_maps                             # gene_body=True: fp32 [len(layers), sum T (* H), max_gene], column 0 = the token itself
     cap.contrib                               # contributions=True: shaped like cap.maps; || sum_h P_h Wo_h v_j ||, what the token RECEIVED
+    cap.gene_contrib                          # gene_contributions=True: shaped like cap.gene_maps; the same norms for the self attention
 
 Who calls what: the model's forward `begin`s the capture with the batch's selected rows (the registry-token rows, the
 only rows the expression head reads); modulator_forward_packed wraps every GENE layer in `cap.layer(i, ...)`; MHA.attend's
 cross branch asks `running()` and, inside a requested gene layer only, hands q and K (with contributions: also V and the
 module's Gram matrix of out_proj, MHA.contrib_gram) to `record`; MHA.attend_qkv and the last
-layer's forward_packed_rows hand the self attention's q and K to `record_self` at the same places.  The CRE layers run
+layer's forward_packed_rows hand the self attention's q and K (and V and the packed out_proj weight, which only the gene-body
+contributions read) to `record_self` at the same places.  The CRE layers run
 outside any `layer(...)` block and are never captured.  DESIGN.md section 5b.
 """
 from __future__ import annotations
@@ -31,7 +33,8 @@ _CAP: contextvars.ContextVar = contextvars.ContextVar("vf_attn_capture", default
 
 
 class Capture:
-    def __init__(self, layers, per_head: bool = False, gene_body: bool = False, contributions: bool = False):
+    def __init__(self, layers, per_head: bool = False, gene_body: bool = False, contributions: bool = False,
+                 gene_contributions: bool = False):
         self.layers = tuple(int(i) for i in layers)     # distinct gene-layer indices, in the order of the first axis of `maps`
         if not self.layers or len(set(self.layers)) != len(self.layers):
             raise ValueError(f"attention maps: a capture needs distinct gene layers, got {list(self.layers)}")
@@ -40,6 +43,9 @@ class Capture:
         self.contributions = bool(contributions)
         self.contrib = None       # contributions: fp32, shaped like `maps`: the value-weighted norms of the most recent forward
         self._scratch = None      # contributions: (gram fp32 [keys, H, H], per-head P fp32 [R * H, max_k] | None), one per forward
+        self.gene_contributions = bool(gene_contributions)
+        self.gene_contrib = None  # gene_contributions: fp32, shaped like `gene_maps`: the self attention's value-weighted norms
+        self._self_scratch = None  # gene_contributions: per-head P fp32 [R * H, max_gene] when the gene map itself is not it
         self.maps = None          # fp32 [len(layers), R or R * H, max_k] of the most recent forward
         self.gene_maps = None     # gene_body: fp32 [len(layers), R or R * H, max_gene] of the most recent forward
         self.shape = None         # the forward's (tissues, cCREs, chunks) per gene: how the rows and columns split (host lists)
@@ -61,6 +67,8 @@ class Capture:
         self.gene_maps = None
         self.contrib = None
         self._scratch = None
+        self.gene_contrib = None
+        self._self_scratch = None
 
     def layer(self, i: int, compact: bool = False):
         """with cap.layer(i): gene layer i is running.  compact: its cross attention's query buffer already is the selected rows,
@@ -96,22 +104,42 @@ class Capture:
         ops.attn_contrib(v, s_gram, probs, cu_rows, cu_k, max_rows, max_k, n_heads, head_dim, gram=gram, out=self.contrib[slot],
                          per_head=self.per_head, family=family + "_contrib")
 
-    def record_self(self, q, k, n_heads: int, head_dim: int, slopes=None, rows=None, family: str = "") -> None:
+    def record_self(self, q, k, n_heads: int, head_dim: int, slopes=None, rows=None, family: str = "", v=None, wo=None) -> None:
         """The running gene layer's SELF attention: q / k its 16-bit query and key operands, slopes its ALiBi slopes (None: a
-        model built without), rows int64 [tokens]: q and k are a table of distinct projected rows and token t's row is
-        rows[t] (the first gene layer).  The selected rows are registry tokens: position 0 of their sequences."""
+        model built without), rows int64 [tokens]: q and k (and v) are a table of distinct projected rows and token t's row is
+        rows[t] (the first gene layer).  The selected rows are registry tokens: position 0 of their sequences, one per
+        sequence.  v / wo: the value operand the attention kernel reads and the 16-bit out_proj weight the GEMM multiplies;
+        only gene_contributions reads them: the per-head P (the gene map itself with per_head and gene_body, else a second
+        call into a scratch; the head-mean gene map keeps its call and bits) feeds ops.attn_contrib_self.  The scratch and
+        gene_contrib are made once per forward and shared by the layers."""
         slot, compact = self._running
         cu_rows, cu_k, max_k = self._self
         q_rows = None if compact else self._rows[0]
         n_out = self.n_rows * (n_heads if self.per_head else 1)
-        if self.gene_maps is None:
+        if self.gene_body and self.gene_maps is None:
             self.gene_maps = torch.empty((len(self.layers), n_out, max_k), dtype=torch.float32, device=q.device)
         if compact:
             assert q.shape[0] == self.n_rows and rows is None
         elif rows is not None:
             q_rows = rows[q_rows]
-        ops.attn_probs(q, k, cu_rows, cu_k, 1, max_k, n_heads, head_dim, q_rows=q_rows, q_log2=True, per_head=self.per_head,
-                       out=self.gene_maps[slot], family=family + "_maps", slopes=slopes, q_pos=None, k_rows=rows)
+        if self.gene_body:
+            ops.attn_probs(q, k, cu_rows, cu_k, 1, max_k, n_heads, head_dim, q_rows=q_rows, q_log2=True, per_head=self.per_head,
+                           out=self.gene_maps[slot], family=family + "_maps", slopes=slopes, q_pos=None, k_rows=rows)
+        if not self.gene_contributions:
+            return
+        assert cu_rows.numel() - 1 == self.n_rows           # one selected row per sequence: row s belongs to sequence s
+        if self.gene_contrib is None:
+            self.gene_contrib = torch.empty((len(self.layers), n_out, max_k), dtype=torch.float32, device=q.device)
+            if not (self.per_head and self.gene_body):
+                self._self_scratch = torch.empty((self.n_rows * n_heads, max_k), dtype=torch.float32, device=q.device)
+        if self.per_head and self.gene_body:
+            probs = self.gene_maps[slot]
+        else:
+            probs = self._self_scratch
+            ops.attn_probs(q, k, cu_rows, cu_k, 1, max_k, n_heads, head_dim, q_rows=q_rows, q_log2=True, per_head=True,
+                           out=probs, family=family + "_gene_contrib", slopes=slopes, q_pos=None, k_rows=rows)
+        ops.attn_contrib_self(v, wo, probs, cu_k, max_k, n_heads, head_dim, out=self.gene_contrib[slot], per_head=self.per_head,
+                              v_rows=rows, family=family + "_gene_contrib")
 
 
 class _Layer:
@@ -173,18 +201,21 @@ def running() -> Capture | None:
 
 
 def running_self() -> Capture | None:
-    """running(), when the capture also asked for the gene-body maps and its forward has named the self-attention grouping."""
+    """running(), when the capture also asked for the gene-body maps or the gene-body contributions and its forward has named
+    the self-attention grouping."""
     cap = running()
-    return cap if cap is not None and cap.gene_body and cap._self is not None else None
+    return cap if cap is not None and (cap.gene_body or cap.gene_contributions) and cap._self is not None else None
 
 
 class capture:
-    """with attn_maps.capture(layers, per_head, gene_body, contributions) as cap: every forward inside records the requested
-    gene layers' maps (gene_body: also those of the self attention over the gene body; contributions: also the value-weighted
-    norms of the cross attention, cap.contrib)."""
+    """with attn_maps.capture(layers, per_head, gene_body, contributions, gene_contributions) as cap: every forward inside
+    records the requested gene layers' maps (gene_body: also those of the self attention over the gene body; contributions:
+    also the value-weighted norms of the cross attention, cap.contrib; gene_contributions: those of the self attention,
+    cap.gene_contrib, with or without gene_body)."""
 
-    def __init__(self, layers, per_head: bool = False, gene_body: bool = False, contributions: bool = False):
-        self.cap = Capture(layers, per_head, gene_body, contributions)
+    def __init__(self, layers, per_head: bool = False, gene_body: bool = False, contributions: bool = False,
+                 gene_contributions: bool = False):
+        self.cap = Capture(layers, per_head, gene_body, contributions, gene_contributions)
 
     def __enter__(self) -> Capture:
         self.token = _CAP.set(self.cap)

@@ -2302,3 +2302,218 @@ extern "C" int vf_attn_contrib(const void* v, int64_t v_stride, const float* s_g
     return H <= 4 ? launch_contrib_norm<4>(P, st) : H <= 8 ? launch_contrib_norm<8>(P, st)
          : H <= 16 ? launch_contrib_norm<16>(P, st) : launch_contrib_norm<32>(P, st);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// vf_attn_contrib_self (include/vf_hip_gene_contrib.h): the same norms for a SELF attention with one selected row per sequence
+// (the gene-body maps: the registry token over its own sequence), in the direct form.  Every key belongs to one row there, so
+// a per-key Gram matrix would be shared by nobody; c[s, j, :] = sum_h P[s, h, j] * Wo_h v[t, h, :] is formed instead, a
+// head-scaled GEMM [keys, H dh] x [H dh, Do] whose rows are reduced to their norms and never stored.
+//   one block  = one sequence x 256 keys (8 waves x 32 keys); the keys are the MFMA's N dimension, so a lane owns ONE key (and
+//                the accumulator's 16 registers are 16 rows d of c): its value fragments are 16-byte loads from the key's own
+//                row (through v_rows when given), its P[s, h, j] one scalar, and no operand is shared between keys.
+//   K loop     = (group of ND 32-row tiles of Wo) x (head), heads inside: the head's [32 ND, dh] slice of Wo is staged in LDS
+//                once per block (register prefetch of the next slice under the MFMAs), every wave multiplies it with its keys'
+//                value fragments into a ZEROED tile (dh / 16 v_mfma_f32_32x32x16: the exact fp32 product of the 16-bit
+//                operands), then acc += p * tile, one v_fma_f32 per register.  After the last head the group's squares are
+//                added to the key's sum in register order; after the last group the two lane halves are added and the root
+//                taken.  per_head needs no acc: heads outside, groups inside, the squares of the zeroed tile summed directly.
+// fp32 throughout after the 16-bit loads; no atomics; a key's arithmetic touches its own lane pair alone (the MFMA's columns
+// are independent), in an order fixed by (group, head, tile, register), so the bits depend on P[s, :, j], value row t and wo
+// alone.  Lanes past the sequence's keys hold zero fragments and p = 0, read nothing, and store the zeros of their columns.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct ContribSelfParams {
+    const unsigned short* v;
+    int64_t v_stride;
+    const int64_t* v_rows;
+    const unsigned short* wo;
+    int64_t ldw;
+    const float* probs;
+    int64_t ldp;
+    const int32_t* cu_k;
+    int H, Do, max_k, n_tiles;
+    float* out;
+    int64_t ldo;
+};
+
+constexpr int CS_KEYS = 256;        // keys per block: 32 per wave
+// 32-row tiles of Wo per group: the accumulators (16 registers each) and the LDS slice [32 ND, dh] set it
+template <int DH> constexpr int cs_nd() { return DH <= 64 ? 8 : 4; }
+// LDS row stride in elements: dh + 8 puts the 16 rows of a ds_read_b128 group in 16 different bank quads for every dh
+template <int DH> constexpr int cs_ls() { return DH + 8; }
+
+template <int DT, int DH, bool PER_HEAD>
+__global__ __launch_bounds__(512) void attn_contrib_self_kernel(ContribSelfParams P) {
+    using frag = typename Op16<DT>::frag;
+    constexpr int ND = cs_nd<DH>(), LS = cs_ls<DH>(), KS = DH / 16, ROWS = 32 * ND, CPR = DH / 8, NCH = ROWS * CPR / 512;
+    static_assert(ROWS * CPR % 512 == 0, "the Wo slice is a whole number of 16-byte chunks per thread");
+    __shared__ __attribute__((aligned(16))) unsigned short W[ROWS * LS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hl = lane >> 5;
+    const int seq = (int)(blockIdx.x / (unsigned)P.n_tiles), tile = (int)(blockIdx.x % (unsigned)P.n_tiles);
+    const int k0 = P.cu_k[seq], len_k = P.cu_k[seq + 1] - k0;
+    const int H = P.H;
+    const int j = tile * CS_KEYS + wave * 32 + r;
+    const bool valid = j < len_k;
+    if (!valid && j < P.max_k && hl == 0) {                       // past the sequence's keys: zeros
+        if (PER_HEAD) for (int h = 0; h < H; ++h) P.out[((int64_t)seq * H + h) * P.ldo + j] = 0.f;
+        else P.out[(int64_t)seq * P.ldo + j] = 0.f;
+    }
+    if (tile * CS_KEYS >= len_k) return;                          // block-uniform
+    const bool wave_active = tile * CS_KEYS + wave * 32 < len_k;  // wave-uniform: a wave without keys only helps staging Wo
+
+    const unsigned short* vp = P.v;
+    if (valid) {
+        const int64_t t = (int64_t)k0 + j;
+        vp += (P.v_rows ? P.v_rows[t] : t) * P.v_stride + 8 * hl;
+    }
+    const float* pp = P.probs + (int64_t)seq * H * P.ldp + j;
+    const int n_dt = P.Do / 32, NG = (n_dt + ND - 1) / ND, n_it = NG * H;
+
+    u32x4_t wreg[NCH];
+    auto load_wo = [&](int g, int h) {
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int q = tid + 512 * i, row = q / CPR, c = q % CPR, d = g * ROWS + row;
+            wreg[i] = (u32x4_t){0u, 0u, 0u, 0u};                  // rows past Do (a partial last group): zeros, never used
+            if (d < P.Do) wreg[i] = *reinterpret_cast<const u32x4_t*>(P.wo + (int64_t)d * P.ldw + h * DH + 8 * c);
+        }
+    };
+    auto store_wo = [&]() {
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int q = tid + 512 * i, row = q / CPR, c = q % CPR;
+            *reinterpret_cast<u32x4_t*>(W + row * LS + 8 * c) = wreg[i];
+        }
+    };
+    auto load_v = [&](int h, u32x4_t (&dst)[KS]) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            dst[s] = (u32x4_t){0u, 0u, 0u, 0u};
+            if (valid) dst[s] = *reinterpret_cast<const u32x4_t*>(vp + h * DH + 16 * s);
+        }
+    };
+    auto it_g = [&](int it) { return PER_HEAD ? it % NG : it / H; };
+    auto it_h = [&](int it) { return PER_HEAD ? it / NG : it % H; };
+
+    u32x4_t vcur[KS], vnext[KS];
+    float pcur = 0.f, pnext = 0.f;
+    load_wo(it_g(0), it_h(0));
+    load_v(it_h(0), vcur);
+    if (valid) pcur = pp[(int64_t)it_h(0) * P.ldp];
+    store_wo();
+    __syncthreads();
+
+    f32x16_t acc[ND];
+    float nsq = 0.f;                                               // the key's sum of squares (PER_HEAD: of the running head)
+    for (int it = 0; it < n_it; ++it) {
+        const int g = it_g(it), h = it_h(it);
+        const bool more = it + 1 < n_it;
+        if (more) {
+            const int g2 = it_g(it + 1), h2 = it_h(it + 1);
+            load_wo(g2, h2);
+            load_v(h2, vnext);
+            pnext = valid ? pp[(int64_t)h2 * P.ldp] : 0.f;
+        }
+        if (wave_active) {
+#pragma unroll
+            for (int dt = 0; dt < ND; ++dt) {
+                if (g * ND + dt < n_dt) {                         // block-uniform
+                    f32x16_t tmp;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) tmp[i] = 0.f;
+#pragma unroll
+                    for (int s = 0; s < KS; ++s) {
+                        const frag a = *reinterpret_cast<const frag*>(W + (dt * 32 + r) * LS + 16 * s + 8 * hl);
+                        tmp = Op16<DT>::mfma32(a, __builtin_bit_cast(frag, vcur[s]), tmp);
+                    }
+                    if (PER_HEAD) {
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) nsq = __builtin_fmaf(tmp[i], tmp[i], nsq);
+                    } else {
+                        if (h == 0) {
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
+                        }
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) acc[dt][i] = __builtin_fmaf(pcur, tmp[i], acc[dt][i]);
+                    }
+                }
+            }
+            if (!PER_HEAD && h == H - 1) {
+#pragma unroll
+                for (int dt = 0; dt < ND; ++dt)
+                    if (g * ND + dt < n_dt) {
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) nsq = __builtin_fmaf(acc[dt][i], acc[dt][i], nsq);
+                    }
+            }
+            if (PER_HEAD && g == NG - 1) {
+                const float tot = nsq + __shfl_xor(nsq, 32);
+                if (valid && hl == 0) P.out[((int64_t)seq * H + h) * P.ldo + j] = pcur * __builtin_sqrtf(tot);
+                nsq = 0.f;
+            }
+        }
+        __syncthreads();                                          // every wave has read this slice
+        if (more) store_wo();
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < KS; ++s) vcur[s] = vnext[s];
+        pcur = pnext;
+    }
+    if (!PER_HEAD && wave_active) {
+        const float tot = nsq + __shfl_xor(nsq, 32);
+        if (valid && hl == 0) P.out[(int64_t)seq * P.ldo + j] = __builtin_sqrtf(tot);
+    }
+}
+
+template <int DT, int DH>
+static int launch_contrib_self(const ContribSelfParams& P, unsigned blocks, int per_head, hipStream_t st) {
+    if (per_head) hipLaunchKernelGGL((attn_contrib_self_kernel<DT, DH, true>), dim3(blocks), dim3(512), 0, st, P);
+    else hipLaunchKernelGGL((attn_contrib_self_kernel<DT, DH, false>), dim3(blocks), dim3(512), 0, st, P);
+    VF_CHECK_LAUNCH("vf_attn_contrib_self");
+    return VF_OK;
+}
+
+}  // namespace
+
+extern "C" int vf_attn_contrib_self(const void* v, int64_t v_stride, const int64_t* v_rows, const void* wo, int64_t ldw,
+                                    const float* probs, int64_t ldp, const int32_t* cu_seqlens_k, int n_seq, int max_seqlen_k,
+                                    int H, int dh, int Do, int operand_dtype, int per_head, float* out, int64_t ldo, void* stream) {
+    const char* null_arg = !v ? "v" : !wo ? "wo" : !probs ? "probs" : !cu_seqlens_k ? "cu_seqlens_k" : !out ? "out" : nullptr;
+    VF_REQUIRE(!null_arg, "vf_attn_contrib_self: null pointer %s", null_arg);
+    VF_REQUIRE(operand_dtype == VF_BF16 || operand_dtype == VF_F16, "vf_attn_contrib_self: operand_dtype must be VF_BF16 or VF_F16");
+    VF_REQUIRE(legacy_dh(dh), "vf_attn_contrib_self: head_dim dh=%d not supported (32/48/64/96/128)", dh);
+    VF_REQUIRE(Do > 0 && Do % 32 == 0, "vf_attn_contrib_self: Do=%d must be a positive multiple of 32", Do);
+    VF_REQUIRE(H > 0 && H <= 1024, "vf_attn_contrib_self: H=%d out of range (1 .. 1024: H * dh is a 32-bit column offset)", H);
+    VF_REQUIRE(n_seq >= 0 && max_seqlen_k >= 0, "vf_attn_contrib_self: n_seq=%d max_seqlen_k=%d out of range", n_seq, max_seqlen_k);
+    VF_REQUIRE(ldo >= max_seqlen_k, "vf_attn_contrib_self: ldo=%ld is below max_seqlen_k=%d", (long)ldo, max_seqlen_k);
+    VF_REQUIRE(ldp >= max_seqlen_k, "vf_attn_contrib_self: ldp=%ld is below max_seqlen_k=%d", (long)ldp, max_seqlen_k);
+    VF_REQUIRE(v_stride >= (int64_t)H * dh && v_stride % 8 == 0,
+               "vf_attn_contrib_self: v_stride=%ld must hold H * dh = %d elements and be a multiple of 8", (long)v_stride, H * dh);
+    VF_REQUIRE(ldw >= (int64_t)H * dh && ldw % 8 == 0,
+               "vf_attn_contrib_self: ldw=%ld must hold H * dh = %d elements and be a multiple of 8", (long)ldw, H * dh);
+    VF_REQUIRE((uintptr_t)v % 16 == 0, "vf_attn_contrib_self: v must be 16-byte aligned");
+    VF_REQUIRE((uintptr_t)wo % 16 == 0, "vf_attn_contrib_self: wo must be 16-byte aligned");
+    VF_REQUIRE((uintptr_t)v_rows % 8 == 0, "vf_attn_contrib_self: v_rows must be 8-byte aligned");
+    VF_REQUIRE((uintptr_t)probs % 4 == 0, "vf_attn_contrib_self: probs must be 4-byte aligned");
+    VF_REQUIRE((uintptr_t)out % 4 == 0, "vf_attn_contrib_self: out must be 4-byte aligned");
+    VF_REQUIRE((uintptr_t)cu_seqlens_k % 4 == 0, "vf_attn_contrib_self: cu_seqlens_k must be 4-byte aligned");
+    const long n_tiles = ((long)max_seqlen_k + CS_KEYS - 1) / CS_KEYS;
+    VF_REQUIRE((long)n_seq * n_tiles < (1L << 31),
+               "vf_attn_contrib_self: n_seq=%d max_seqlen_k=%d exceed the grid limit", n_seq, max_seqlen_k);
+    vf_note_kernel(1, "attn_contrib_self_kernel");
+    if (n_seq == 0 || max_seqlen_k == 0) return VF_OK;
+    ContribSelfParams P;
+    P.v = (const unsigned short*)v; P.v_stride = v_stride; P.v_rows = v_rows; P.wo = (const unsigned short*)wo; P.ldw = ldw;
+    P.probs = probs; P.ldp = ldp; P.cu_k = cu_seqlens_k; P.H = H; P.Do = Do; P.max_k = max_seqlen_k; P.n_tiles = (int)n_tiles;
+    P.out = out; P.ldo = ldo;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((long)n_seq * n_tiles);
+#define VF_CS(DT_) (dh == 32 ? launch_contrib_self<DT_, 32>(P, blocks, per_head, st) : dh == 48 ? launch_contrib_self<DT_, 48>(P, blocks, per_head, st) : \
+                    dh == 64 ? launch_contrib_self<DT_, 64>(P, blocks, per_head, st) : dh == 96 ? launch_contrib_self<DT_, 96>(P, blocks, per_head, st) : \
+                    launch_contrib_self<DT_, 128>(P, blocks, per_head, st))
+    const int rc = operand_dtype == VF_BF16 ? VF_CS(VF_BF16) : VF_CS(VF_F16);
+#undef VF_CS
+    return rc;
+}

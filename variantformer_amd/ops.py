@@ -638,6 +638,47 @@ def attn_contrib(v: torch.Tensor, s_gram: torch.Tensor, probs: torch.Tensor, cu_
     return out
 
 
+def attn_contrib_self(v: torch.Tensor, wo: torch.Tensor, probs: torch.Tensor, cu_k: torch.Tensor, max_k: int, n_heads: int,
+                      head_dim: int, out: torch.Tensor, per_head: bool = False, v_rows: torch.Tensor | None = None,
+                      family: str = ""):
+    """Value-weighted norms beside a SELF attention map with one selected row per sequence (vf_attn_contrib_self,
+    include/vf_hip_gene_contrib.h): out[s, j] = || sum_h P[s, h, j] * Wo_h v[t, h] ||_2, t = cu_k[s] + j, or per head
+    out[s * H + h, j] = P[s, h, j] * || Wo_h v[t, h] ||_2.  v [*, >= H*dh] 16-bit row-strided view (the value rows the attention
+    kernel reads); v_rows int64 [keys] or None: key t is row v_rows[t] of v; wo 16-bit [Do, >= H*dh] row-strided, out_proj's
+    weight as packed_linear returns it; probs fp32 [n_seq * H, >= max_k] = ops.attn_probs(per_head=True) with one row per
+    sequence.  The caller owns every buffer, nothing is made here and the kernel needs no workspace: out fp32 [n_seq or
+    n_seq * H, >= max_k].  Columns past a sequence's keys are 0, columns >= max_k are left alone.  Returns out."""
+    _dev(v, wo, probs, cu_k, out)
+    assert _is16(v.dtype) and v.dim() == 2 and v.stride(1) == 1
+    assert wo.dtype == v.dtype and wo.dim() == 2 and wo.stride(1) == 1
+    assert cu_k.dtype == torch.int32 and cu_k.dim() == 1
+    H, dh = int(n_heads), int(head_dim)
+    n_seq = cu_k.numel() - 1
+    for t in (probs, out):
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] >= max_k
+    assert probs.shape[0] == n_seq * H and out.shape[0] == (n_seq * H if per_head else n_seq)
+    if v_rows is not None:
+        _dev(v_rows)
+        assert v_rows.dtype == torch.int64 and v_rows.dim() == 1 and v_rows.is_contiguous()
+    Do = wo.shape[0]
+
+    def launch():
+        check(_lib.load().vf_attn_contrib_self(v.data_ptr(), v.stride(0), 0 if v_rows is None else v_rows.data_ptr(),
+                                               wo.data_ptr(), wo.stride(0), probs.data_ptr(), probs.stride(0), cu_k.data_ptr(),
+                                               n_seq, int(max_k), H, dh, Do, _dt(v.dtype), int(bool(per_head)), out.data_ptr(),
+                                               out.stride(0), _stream()), "vf_attn_contrib_self")
+
+    def keys():
+        return float(cu_k[-1].item()) if n_seq > 0 else 0.0
+    # algorithmic bytes: every value row and P once, wo once, out once (the kernel re-reads v once per group of Wo tiles and
+    # wo once per block; both are traffic of the tiling, not of the problem)
+    _run(launch, lambda: ("attn_contrib_self", lambda: 2.0 * keys() * H * dh * Do,
+                          2.0 * keys() * H * dh + 2.0 * Do * H * dh + 4.0 * n_seq * H * int(max_k) + 4.0 * out.shape[0] * int(max_k),
+                          f"H={H} dh={dh} Do={Do} max_k={int(max_k)}" + (" per_head" if per_head else "") + (" rows" if v_rows is not None else ""),
+                          family or _SCOPE))
+    return out
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

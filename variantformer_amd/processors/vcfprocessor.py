@@ -137,7 +137,7 @@ class VCFProcessor:
         return self.format_output(vcf_dataset.query_df, predictions)
 
     def predict_with_attention(self, model, checkpoint_path, trainer, dataloader, vcf_dataset, layers=None, per_head=False,
-                               gene_body=False, contributions=False):
+                               gene_body=False, contributions=False, gene_contributions=False):
         """`predict`'s frame plus the gene -> cCRE attention maps of the same forwards (no reference counterpart: flash-attn
         returns no probabilities).  New columns, one entry per gene:
           cre_attention         fp32 [len(layers), tissues, cCREs] (per_head: [len(layers), tissues, heads, cCREs]) -- how much the
@@ -157,12 +157,18 @@ class VCFProcessor:
                                 registry token through the cross attention's output projection (value-weighted: a window with
                                 a large weight and a value near zero moves the token less than its weight suggests); the
                                 quantity to rank cCREs by.
+        gene_contributions=True adds (with or without gene_body)
+          gene_contribution     fp32, shaped and ordered like gene_attention -- the same norm through the SELF attention's output
+                                projection: column 0 is what the registry token's own value adds, column 1 + c what gene-body
+                                chunk c (gene_chunk_table) adds; the quantity to rank chunks by, comparable with cre_contribution.
         A plain loop over the loader (the maps are read back per batch)."""
         model.trainer = trainer
         model.eval()
         kw = {"gene_body": True} if gene_body else {}
         if contributions:
             kw["contributions"] = True
+        if gene_contributions:
+            kw["gene_contributions"] = True
         predictions = [model.predict_step_with_attention(batch, i, layers=layers, per_head=per_head, **kw)
                        for i, batch in enumerate(dataloader)]
         try:       # as Trainer.predict: what the self-healing LayerNorm fold did during this pass
@@ -183,9 +189,12 @@ class VCFProcessor:
                 df[col] = pd.Series([t[src].tolist() for t in tables], index=df.index, dtype=object)
         if contributions:
             df["cre_contribution"] = pd.Series([m for p in predictions for m in p["cre_contribution"]], index=df.index, dtype=object)
-        if gene_body:
-            gmaps = [m for p in predictions for m in p["gene_attention"]]
-            df["gene_attention"] = pd.Series(gmaps, index=df.index, dtype=object)
+        if gene_body or gene_contributions:
+            gmaps = []
+            for key, on in (("gene_attention", gene_body), ("gene_contribution", gene_contributions)):
+                if on:
+                    gmaps = [m for p in predictions for m in p[key]]
+                    df[key] = pd.Series(gmaps, index=df.index, dtype=object)
             if hasattr(vcf_dataset, "gene_chunk_table"):
                 tables = [vcf_dataset.gene_chunk_table(g) for g in df["gene_id"]]
                 for g, t, m in zip(df["gene_id"], tables, gmaps):    # a row per map column behind the registry token's

@@ -966,7 +966,7 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
                                       "evaluation order of the options the shipped configuration leaves off)")
 
     def predict_step_with_attention(self, batch, batch_idx, dataloader_idx=None, layers=None, per_head=False, gene_body=False,
-                                    contributions=False):
+                                    contributions=False, gene_contributions=False):
         """predict_step's dict plus the attention maps of the registry tokens in the same forward:
           "cre_attention"         per gene, fp32 numpy [len(layers), T_i, N_i] -- the head mean of the softmax of gene layer
                                   `layers[k]`'s cross attention on the registry-token row of tissue t (tissues in the order of
@@ -981,6 +981,11 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
                                   || sum_h P[h, j] Wo_h v[j, h] || (per_head: P[h, j] || Wo_h v[j, h] ||, head h's own share):
                                   what the token received, where "cre_attention" says where it looked.  Predictions and the
                                   maps keep their bits with it.
+          "gene_contribution"     with gene_contributions (with or without gene_body): per gene, fp32 numpy shaped like
+                                  "gene_attention" -- the same norm for the SELF attention's out_proj: column 0 is what the
+                                  token's own value adds to it, column 1 + c what gene-body chunk c adds.  ALiBi hands nearby
+                                  chunks weight whatever their values are; this is the quantity to rank chunks by, and the one
+                                  comparable with "cre_contribution".  Everything else keeps its bits with it.
         layers: distinct gene-layer indices (negative: from the end; None: all; ValueError for an index out of range, an empty
         list or a layer named twice).  When the batch trips the LayerNorm-fold alert the
         recomputation runs under the capture too and the maps are its maps.  A vep model has
@@ -988,20 +993,22 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
         self.eval()
         self._attention_maps_supported()
         sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
-        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions) as cap:
+        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions, gene_contributions) as cap:
             out = self.predict_finish(self.predict_launch(self.prepare_batch(batch)), batch_idx, dataloader_idx)
             return self._with_attention(out, cap)         # the recomputation's maps when predict_finish healed the batch
 
-    def variant_prediction_with_attention(self, batch, layers=None, per_head=False, gene_body=False, contributions=False):
+    def variant_prediction_with_attention(self, batch, layers=None, per_head=False, gene_body=False, contributions=False,
+                                          gene_contributions=False):
         """variant_prediction's dict (bit for bit) plus "cre_attention", "cre_attention_layers" and, with gene_body /
-        contributions, "gene_attention" / "cre_contribution" as predict_step_with_attention describes them, with one entry per
+        contributions / gene_contributions, "gene_attention" / "cre_contribution" / "gene_contribution" as
+        predict_step_with_attention describes them, with one entry per
         genotype of the batch, in batch order: ref, het, hom -- how a variant moved the model's attention.  The VEP forward keeps the full last gene layer (it
         reads token-position rows of it), so every layer records through the row map of the registry rows.  When the batch
         trips the LayerNorm-fold alert the recomputation runs under the capture too and the maps are its maps."""
         self.eval()
         self._attention_maps_supported(vep_ok=True)
         sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
-        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions) as cap:
+        with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions, gene_contributions) as cap:
             return self._with_attention(self.variant_prediction(batch), cap)
 
     def _with_attention(self, out: dict, cap) -> dict:
@@ -1027,6 +1034,8 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
             out["gene_attention"] = per_gene(cap.gene_maps, [1 + c for c in cap.shape[2]] if cap.shape else [])
         if cap.contributions:
             out["cre_contribution"] = per_gene(cap.contrib, cap.shape[1] if cap.shape else [])
+        if cap.gene_contributions:
+            out["gene_contribution"] = per_gene(cap.gene_contrib, [1 + c for c in cap.shape[2]] if cap.shape else [])
         return out
 
     def predict_launch(self, pb: PreparedBatch) -> PredictHandle:

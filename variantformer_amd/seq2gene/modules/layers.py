@@ -434,8 +434,12 @@ class MHA(nn.Module):
             qkv, rows = ops.gather_rows_bf16(qkv, rows), None
         cap = attn_maps.running_self()     # a requested gene layer's self attention under capture(gene_body=True): its P, in fp32
         if cap is not None:
-            cap.record_self(qkv[:, :D], qkv[:, D:2 * D], self.num_heads, self.head_dim, self.alibi_slopes, rows=rows,
-                            family=self.family)
+            if cap.gene_contributions:      # also V (behind the same row map) and the out_proj weight the GEMM multiplies
+                cap.record_self(qkv[:, :D], qkv[:, D:2 * D], self.num_heads, self.head_dim, self.alibi_slopes, rows=rows,
+                                family=self.family, v=qkv[:, 2 * D:], wo=packed_linear(self.out_proj)[0])
+            else:
+                cap.record_self(qkv[:, :D], qkv[:, D:2 * D], self.num_heads, self.head_dim, self.alibi_slopes, rows=rows,
+                                family=self.family)
         return ops.attn_varlen(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], cu_q, None, max_q, max_q,
                                self.num_heads, self.head_dim, self.alibi_slopes, family=self.family,
                                q_log2=True, rows=rows)
@@ -657,7 +661,11 @@ class ContextFlashAttentionEncoderLayer(nn.Module):
         q = mha.project_qkv(hr, self.norm1, out_rows=slice(0, D))                  # [R, D]
         cap = attn_maps.running_self()
         if cap is not None:                                                        # q already is the registry rows (compact)
-            cap.record_self(q, kv[:, :D], mha.num_heads, mha.head_dim, mha.alibi_slopes, family=mha.family + "_registry_rows")
+            if cap.gene_contributions:
+                cap.record_self(q, kv[:, :D], mha.num_heads, mha.head_dim, mha.alibi_slopes, family=mha.family + "_registry_rows",
+                                v=kv[:, D:], wo=packed_linear(mha.out_proj)[0])
+            else:
+                cap.record_self(q, kv[:, :D], mha.num_heads, mha.head_dim, mha.alibi_slopes, family=mha.family + "_registry_rows")
         a = ops.attn_varlen(q, kv[:, :D], kv[:, D:], cu_rows, cu_src, 1, max_src, mha.num_heads, mha.head_dim,
                             mha.alibi_slopes, q_at_start=True, family=mha.family + "_registry_rows",
                             q_log2=True)
