@@ -668,6 +668,83 @@ __global__ __launch_bounds__(256) void cast_f32_16_kernel(const float* __restric
         out[(n4 << 2) + threadIdx.x] = (unsigned short)(pack2_dt(x[(n4 << 2) + threadIdx.x], 0.f, out_dt) & 0xFFFFu);
 }
 
+// ---------------------------------------------------------------------------------------------
+// tokenizer classifier heads (include/vf_hip_cre_heads.h): a group of Cp = 2^cp_shift >= C adjacent lanes per (sample, tissue)
+// pair (64 / Cp pairs per wave), lane c of the group owns class c.  Every lane walks the F features in ascending order with one
+// fma per term; xbar is the same for the lanes of a group, the weights are one row per lane.  Softmax and argmax are butterflies
+// inside the group.  1e-3 of the encoder's FLOPs on the same windows: written to be exact and position-independent, not fast.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void tissue_heads_kernel(const float* __restrict__ x, int64_t ldx, int ns, int concat,
+                                                          const float* __restrict__ w, const float* __restrict__ bias,
+                                                          int n_tissues, int C, int cp_shift, int d,
+                                                          const int64_t* __restrict__ tissue_of_row,
+                                                          const int32_t* __restrict__ tissues, int n_sel, int64_t n_pairs,
+                                                          int mode, float* __restrict__ out, int64_t ldo,
+                                                          int32_t* __restrict__ argmax) {
+    const int lane = threadIdx.x & 63;
+    const int Cp = 1 << cp_shift;
+    const int cl = lane & (Cp - 1);                                // the lane's class
+    const int64_t first = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) << (6 - cp_shift);
+    if (first >= n_pairs) return;                                  // wave-uniform
+    const int64_t mine = first + (lane >> cp_shift);
+    const bool live = mine < n_pairs;                              // a group past the end repeats the last pair and stores nothing
+    const int64_t pair = live ? mine : n_pairs - 1;
+    int64_t b, t;
+    int i;
+    if (tissue_of_row) { b = pair; i = 0; t = tissue_of_row[b]; }
+    else { b = pair / n_sel; i = (int)(pair - b * n_sel); t = tissues[i]; }
+    const bool has_head = t >= 0 && t < n_tissues;                 // an id without a head: nothing is read, NaN and -1 are written
+    const bool active = cl < C;
+    const float qnan = __uint_as_float(0x7FC00000u);
+    const int F = concat ? ns * d : d;
+    const int n_out = concat ? ns : 1, n_in = concat ? 1 : ns;     // concat: ns runs of d features; mean: one run, ns rows summed
+    const int d4 = d >> 2;
+    const float fns = (float)n_in;
+    float logit = qnan;
+    if (active && has_head) {
+        const float* xb = x + b * ns * ldx;
+        const f32x4_t* wr = reinterpret_cast<const f32x4_t*>(w + (t * C + cl) * F);
+        float acc = 0.f;
+        for (int so = 0; so < n_out; ++so) {
+            const f32x4_t* x0 = reinterpret_cast<const f32x4_t*>(xb + so * ldx);
+            for (int k = 0; k < d4; ++k) {
+                f32x4_t xv = x0[k];
+                for (int s = 1; s < n_in; ++s) {
+                    const f32x4_t xs = reinterpret_cast<const f32x4_t*>(xb + s * ldx)[k];
+                    xv[0] += xs[0]; xv[1] += xs[1]; xv[2] += xs[2]; xv[3] += xs[3];
+                }
+                if (n_in > 1) { xv[0] /= fns; xv[1] /= fns; xv[2] /= fns; xv[3] /= fns; }
+                const f32x4_t wv = wr[so * d4 + k];
+                acc = __builtin_fmaf(xv[0], wv[0], acc);
+                acc = __builtin_fmaf(xv[1], wv[1], acc);
+                acc = __builtin_fmaf(xv[2], wv[2], acc);
+                acc = __builtin_fmaf(xv[3], wv[3], acc);
+            }
+        }
+        logit = acc + bias[t * C + cl];
+    }
+    // over the group: is any logit NaN; the first index of the largest logit ((value, index) butterfly, the smaller index wins a
+    // tie, idle lanes lose every comparison)
+    int nan_seen = active && logit != logit;
+    float mv = active ? logit : -__builtin_inff();
+    int mi = active ? cl : 64;
+    for (int off = Cp >> 1; off > 0; off >>= 1) {
+        nan_seen |= __shfl_xor(nan_seen, off);
+        const float ov = __shfl_xor(mv, off);
+        const int oi = __shfl_xor(mi, off);
+        if (ov > mv || (ov == mv && oi < mi)) { mv = ov; mi = oi; }
+    }
+    float val = logit;
+    if (mode == 1) {
+        const float e = active ? expf(logit - mv) : 0.f;
+        float sum = e;
+        for (int off = Cp >> 1; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        val = nan_seen ? qnan : e / sum;                           // a NaN logit: all C probabilities of this (b, t)
+    }
+    if (live && active) out[b * ldo + (int64_t)i * C + cl] = val;
+    if (live && argmax && cl == 0) argmax[pair] = nan_seen ? -1 : mi;
+}
+
 inline int stream_grid(int64_t work_items) {
     int64_t b = (work_items + 255) / 256;
     if (b < 1) b = 1;
@@ -901,3 +978,44 @@ static int cast_f32_16(const float* x, void* out, int64_t n, int dt, void* strea
 
 extern "C" int vf_cast_f32_bf16(const float* x, void* out, int64_t n, void* stream) { return cast_f32_16(x, out, n, VF_BF16, stream); }
 extern "C" int vf_cast_f32_f16(const float* x, void* out, int64_t n, void* stream) { return cast_f32_16(x, out, n, VF_F16, stream); }
+
+extern "C" int vf_tissue_heads(const float* x, int64_t ldx, int n_strands, int strand_agg, const float* w, const float* bias,
+                               int n_tissues, int C, int d, const int64_t* tissue_of_row, const int32_t* tissues, int n_sel,
+                               int64_t B, int mode, float* out, int64_t ldo, int32_t* argmax, void* stream) {
+    VF_REQUIRE(x, "vf_tissue_heads: null pointer x");
+    VF_REQUIRE(w, "vf_tissue_heads: null pointer w");
+    VF_REQUIRE(bias, "vf_tissue_heads: null pointer bias");
+    VF_REQUIRE(out, "vf_tissue_heads: null pointer out");
+    VF_REQUIRE(d > 0 && d % 4 == 0, "vf_tissue_heads: d=%d must be a positive multiple of 4", d);
+    VF_REQUIRE(C >= 1 && C <= 64, "vf_tissue_heads: C=%d must lie in 1 .. 64", C);
+    VF_REQUIRE(n_strands >= 1 && n_strands <= 8, "vf_tissue_heads: n_strands=%d must lie in 1 .. 8", n_strands);
+    VF_REQUIRE(n_tissues >= 1, "vf_tissue_heads: n_tissues=%d must be positive", n_tissues);
+    VF_REQUIRE(strand_agg == 0 || strand_agg == 1, "vf_tissue_heads: bad strand_agg %d (0 = mean, 1 = concat)", strand_agg);
+    VF_REQUIRE(mode == 0 || mode == 1, "vf_tissue_heads: bad mode %d (0 = logits, 1 = probabilities)", mode);
+    VF_REQUIRE(ldx >= d && ldx % 4 == 0, "vf_tissue_heads: ldx=%ld must be at least d=%d and a multiple of 4", (long)ldx, d);
+    VF_REQUIRE((tissue_of_row != nullptr) != (tissues != nullptr),
+               "vf_tissue_heads: exactly one of tissue_of_row and tissues must be given (%s)", tissues ? "both are" : "neither is");
+    VF_REQUIRE(B >= 0, "vf_tissue_heads: B=%ld must not be negative", (long)B);
+    if (tissue_of_row) n_sel = 1;
+    VF_REQUIRE(n_sel >= 0, "vf_tissue_heads: n_sel=%d must not be negative", n_sel);
+    VF_REQUIRE(ldo >= (int64_t)n_sel * C, "vf_tissue_heads: ldo=%ld is below the %ld values of a row", (long)ldo, (long)n_sel * C);
+    VF_REQUIRE((uintptr_t)x % 16 == 0, "vf_tissue_heads: x must be 16-byte aligned");
+    VF_REQUIRE((uintptr_t)w % 16 == 0, "vf_tissue_heads: w must be 16-byte aligned");
+    VF_REQUIRE((uintptr_t)tissue_of_row % 8 == 0, "vf_tissue_heads: tissue_of_row must be 8-byte aligned");
+    VF_REQUIRE((uintptr_t)bias % 4 == 0, "vf_tissue_heads: bias must be 4-byte aligned");
+    VF_REQUIRE((uintptr_t)out % 4 == 0, "vf_tissue_heads: out must be 4-byte aligned");
+    VF_REQUIRE((uintptr_t)tissues % 4 == 0, "vf_tissue_heads: tissues must be 4-byte aligned");
+    VF_REQUIRE((uintptr_t)argmax % 4 == 0, "vf_tissue_heads: argmax must be 4-byte aligned");
+    if (B == 0 || n_sel == 0) return VF_OK;
+    VF_REQUIRE(B <= (INT64_MAX - 3) / n_sel && (B * n_sel + 3) / 4 < ((int64_t)1 << 31),
+               "vf_tissue_heads: grid of ceil(B * n_sel / 4) blocks (B=%ld n_sel=%d) does not fit 2^31", (long)B, n_sel);
+    const int64_t n_pairs = B * n_sel;
+    int cp_shift = 0;                                       // a group of 2^cp_shift >= C lanes per pair, 64 >> cp_shift pairs per wave
+    while ((1 << cp_shift) < C) ++cp_shift;
+    const int64_t per_block = (int64_t)4 << (6 - cp_shift);
+    hipLaunchKernelGGL(tissue_heads_kernel, dim3((unsigned)((n_pairs + per_block - 1) / per_block)), dim3(256), 0, (hipStream_t)stream,
+                       x, ldx, n_strands, strand_agg, w, bias, n_tissues, C, cp_shift, d, tissue_of_row, tissues, n_sel, n_pairs, mode,
+                       out, ldo, argmax);
+    VF_CHECK_LAUNCH("vf_tissue_heads");
+    return VF_OK;
+}

@@ -679,6 +679,60 @@ def attn_contrib_self(v: torch.Tensor, wo: torch.Tensor, probs: torch.Tensor, cu
     return out
 
 
+def tissue_heads(x: torch.Tensor, n_strands: int, strand_agg, w: torch.Tensor, bias: torch.Tensor,
+                 tissue_of_row: torch.Tensor | None = None, tissues: torch.Tensor | None = None, probabilities: bool = False, *,
+                 out: torch.Tensor, argmax: torch.Tensor | None, checked: bool = False, family: str = ""):
+    """The tokenizer's per-tissue classifier heads (vf_tissue_heads, include/vf_hip_cre_heads.h).  x fp32 [B * n_strands, >= d]
+    row-strided, the strands of a sample adjacent; strand_agg "mean" / "concat" (or 0 / 1); w fp32 [T, C, F] and bias fp32 [T, C]
+    contiguous, F = d or n_strands * d.  Row form: tissue_of_row int64 [B] on the device, sample b through the head of its own
+    tissue -> out fp32 [B, >= C], argmax int32 [B].  All form: tissues int32 [n_sel] on the device, every sample through each of
+    them -> out fp32 [B, >= n_sel * C], argmax int32 [B, n_sel].  Logits, or with probabilities=True the softmax over the
+    classes; argmax is the first largest logit, -1 where a logit is NaN.  The caller owns every buffer and nothing is made here,
+    as in attn_contrib: out (2-D, row stride >= the values of a row; columns past them are left alone) and argmax (contiguous;
+    None: not wanted, none is written) must be passed.  The ids are checked with one read-back of their minimum and maximum (the reference's
+    torch.unique(...).item() loop syncs too), and an id without a head raises KeyError like the reference's ModuleDict lookup;
+    checked=True skips the read-back for ids the caller built from host data it has checked itself (the kernel reads nothing
+    for an id without a head either way).  Returns (out, argmax)."""
+    _dev(x, w, bias, tissue_of_row, tissues, out, argmax)
+    ns = int(n_strands)
+    agg = {"mean": 0, "concat": 1}.get(strand_agg, strand_agg)
+    assert agg in (0, 1), f"strand_agg must be 'mean' or 'concat', not {strand_agg!r}"
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and ns >= 1 and x.shape[0] % ns == 0
+    assert w.dtype == torch.float32 and w.dim() == 3 and w.is_contiguous()
+    T, C, F = w.shape
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and tuple(bias.shape) == (T, C)
+    d = F // ns if agg == 1 else F
+    assert d * (ns if agg == 1 else 1) == F and x.shape[1] >= d
+    B = x.shape[0] // ns
+    if (tissue_of_row is None) == (tissues is None):
+        raise ValueError("tissue_heads takes tissue_of_row (one head per sample) or tissues (every sample through each): "
+                         + ("not both" if tissues is not None else "one of them is required"))
+    if tissue_of_row is not None:
+        assert tissue_of_row.dtype == torch.int64 and tissue_of_row.is_contiguous() and tuple(tissue_of_row.shape) == (B,)
+        ids, n_sel = tissue_of_row, 1
+    else:
+        assert tissues.dtype == torch.int32 and tissues.dim() == 1 and tissues.is_contiguous()
+        ids, n_sel = tissues, tissues.numel()
+    if not checked and ids.numel():
+        lo, hi = torch.stack(torch.aminmax(ids)).tolist()
+        if lo < 0 or hi >= T:
+            raise KeyError(str(lo if lo < 0 else hi))
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == B and out.shape[1] >= n_sel * C
+    assert argmax is None or (argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * n_sel)
+
+    def launch():
+        if B == 0 or n_sel == 0:                      # nothing to do (an empty tensor has no address to hand over)
+            return
+        check(_lib.load().vf_tissue_heads(x.data_ptr(), x.stride(0), ns, agg, w.data_ptr(), bias.data_ptr(), T, C, d,
+                                          _ptr(tissue_of_row), _ptr(tissues), n_sel, B, int(bool(probabilities)),
+                                          out.data_ptr(), out.stride(0), _ptr(argmax), _stream()), "vf_tissue_heads")
+    # algorithmic bytes: x, the heads and the outputs once (the kernel re-reads a head per sample, from L2)
+    _run(launch, lambda: ("tissue_heads", 2.0 * B * n_sel * C * F, 4.0 * (B * ns * d + T * C * (F + 1) + B * n_sel * (C + (argmax is not None))),
+                          f"d={d} C={C} ns={ns} n_sel={n_sel}" + (" concat" if agg else "") + (" rows" if tissue_of_row is not None else ""),
+                          family or _SCOPE))
+    return out, argmax
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

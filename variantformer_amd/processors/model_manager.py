@@ -42,6 +42,29 @@ class ModelManager:
     def _load_seq2reg_gene(self, train_cfg) -> Seq2RegPredictor:
         return self._load_seq2reg_from(train_cfg.gene_tokenizer.path)
 
+    def load_tokenizer(self, which: str = "cre") -> Seq2RegPredictor:
+        """The PRETRAINED tokenizer checkpoint the config names (`cre_tokenizer.path`, or `gene_tokenizer.path` with
+        which="gene"), in eval mode on the device: encoder and per-tissue classifier heads as they were trained together, for
+        Seq2RegPredictor.classify / forward(only_embed=False) / predict_step.
+
+        Deliberately NOT the tokenizer inside the model load_model() returns.  The expression checkpoint overwrites that
+        tokenizer's encoder with weights fine-tuned for expression, while the classifier heads it carries were never trained
+        against the fine-tuned encoder: heads and encoder of the big checkpoint do not belong together.  The pair that does is
+        the one in the tokenizer checkpoint, so that is what is loaded here."""
+        if which not in ("cre", "gene"):
+            raise ValueError(f"which must be 'cre' or 'gene', not {which!r}")
+        if self.device != "cuda":
+            raise RuntimeError("no GPU visible: the HIP inference path has no CPU fallback")
+        cfg = self.config
+        path = (cfg.cre_tokenizer if which == "cre" else cfg.gene_tokenizer).path
+        if not os.path.exists(path):
+            raise ValueError(f"Tokenizer checkpoint not found: {path}")
+        log.info(f"Loading the {which} tokenizer from {path}")
+        tok = self._load_seq2reg_from(path)
+        tok.eval()
+        tok.to(self.device)
+        return tok
+
     def load_model(self) -> Tuple[Seq2GenePredictorCombinedModulator, str]:
         train_cfg = self.config.copy() if hasattr(self.config, "copy") else Config(dict(self.config))
         if not isinstance(train_cfg, Config):

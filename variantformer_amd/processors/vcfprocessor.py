@@ -23,6 +23,12 @@ from .model_manager import ModelManager
 from .trainer import Trainer
 
 
+def cre_class_names(num_classes: int) -> list:
+    """The names of a tokenizer's classes: utils.constants.CREs when its heads have exactly that many, else the indices."""
+    from ..utils.constants import CREs
+    return list(CREs) if num_classes == len(CREs) else list(range(num_classes))
+
+
 class VCFProcessor:
     def __init__(self, model_class: str = "v4_pcg", config_dir: str | None = None, require_gpu: bool = True,
                  gene_cre_manifest=None, indel_policy: str = "bcftools"):
@@ -203,6 +209,48 @@ class VCFProcessor:
                                  ("gene_chunk_start", "start"), ("gene_chunk_end", "end")):
                     df[col] = pd.Series([[None if pd.isna(v) else int(v) for v in t[src]] for t in tables], index=df.index,
                                         dtype=object)
+        return df
+
+    def predict_cre_activity(self, tokenizer, dataloader, vcf_dataset, tissues=None):
+        """What the cCRE tokenizer takes each of a gene's cCRE windows to BE in each of its tissues, for this individual's
+        sequence: the class probabilities of the tokenizer's per-tissue classifier heads.  `tokenizer` is
+        ModelManager.load_tokenizer("cre") -- the pretrained pair of encoder and heads, not the tokenizer inside the expression
+        model, whose encoder was fine-tuned away from its heads.  `tissues`: head indices (default: all).  Returns the query
+        frame with, one entry per gene:
+          cre_class_probabilities   fp32 [cCREs, len(tissues), classes];
+          cre_class                 int [cCREs, len(tissues)]: the most probable class (-1 where a logit is NaN);
+          cre_activity_tissues      the heads' names (the tokenizer's `tissues` hyper-parameter) where it has them, else their
+                                    indices, in the order of axis 1;
+          cre_class_names           the names of the classes (utils.constants.CREs when the heads have that many), else indices;
+          cre_names, cre_start, cre_end   the manifest rows of the windows, where the dataset can name them (cre_table).
+        A plain loop over the loader; the window's reference label is the context of a use_context tokenizer and unused
+        otherwise."""
+        tokenizer.eval()
+        n_heads = len(tokenizer.tissue_classifiers)
+        sel = list(range(n_heads)) if tissues is None else [int(t) for t in tissues]
+        probs, classes = [], []
+        with torch.no_grad():
+            for batch in dataloader:
+                for i, ids in enumerate(batch["cre_sequences"]):
+                    p, c = tokenizer.classify(ids, batch["cre_attention_masks"][i], context=batch["ref_cre_labels"][i],
+                                              tissues=None if tissues is None else sel, probabilities=True)
+                    probs.append(p.cpu().numpy())
+                    classes.append(c.cpu().numpy())
+        df = vcf_dataset.query_df
+        assert len(df) == len(probs), "DataFrame and predictions length mismatch"
+        df["cre_class_probabilities"] = pd.Series(probs, index=df.index, dtype=object)
+        df["cre_class"] = pd.Series(classes, index=df.index, dtype=object)
+        names = getattr(tokenizer, "tissues", None)
+        head_names = [names[t] for t in sel] if names is not None and len(names) == n_heads else list(sel)
+        df["cre_activity_tissues"] = pd.Series([list(head_names) for _ in probs], index=df.index, dtype=object)
+        class_names = cre_class_names(tokenizer.num_classes)
+        df["cre_class_names"] = pd.Series([list(class_names) for _ in probs], index=df.index, dtype=object)
+        if hasattr(vcf_dataset, "cre_table"):
+            tables = [vcf_dataset.cre_table(g) for g in df["gene_id"]]
+            for g, t, p in zip(df["gene_id"], tables, probs):           # a name per window, or no names at all
+                assert len(t) == p.shape[0], f"{g}: cre_table names {len(t)} windows, {p.shape[0]} were classified"
+            for col, src in (("cre_names", "cre_name"), ("cre_start", "start_cre"), ("cre_end", "end_cre")):
+                df[col] = pd.Series([t[src].tolist() for t in tables], index=df.index, dtype=object)
         return df
 
     def predict_distributed(self, model, checkpoint_path, trainer, vcf_dataset, batch_size: int | None = None, costs=None,

@@ -3,8 +3,9 @@
 Same constructor arguments, hyper-parameter record and state-dict keys as the reference
 (seq2reg/model.py:40-191) so that `Seq2RegPredictor(**chk["hyper_parameters"])` followed by
 `load_state_dict(chk["state_dict"])` works unchanged (processors/model_manager.py:44-51).
-Only the inference path the hot loop uses is implemented: forward(only_embed=True)
-(seq2reg/model.py:193-279).  Training / classification heads are out of scope.
+The inference paths are implemented: forward(only_embed=True), the hot loop's (seq2reg/model.py:193-279), and the per-tissue
+classifier heads behind it (forward(only_embed=False), predict_step, :274-302, :440-449; classify is the all-tissue form).
+Training, losses and metric logging are out of scope.
 """
 from __future__ import annotations
 
@@ -92,7 +93,7 @@ class Seq2RegPredictor(nn.Module):
                 [FlashTransformerLayer(d_model=embedding_dim, nhead=num_heads, use_alibi=use_alibi) for _ in range(num_layers)])
         if seq_pool == "linear":              # :183-184
             self.linear = nn.Linear(token_length, 1)
-        # kept only so that checkpoints load strictly; unused at inference
+        # the per-tissue cCRE class heads (reference :186-191); run by ops.tissue_heads on the stacked copy of _stacked_heads
         in_f = embedding_dim * 2 if strand_agg == "concat" else embedding_dim
         self.tissue_classifiers = nn.ModuleDict({str(t): nn.Linear(in_f, num_classes) for t in range(num_tissues)})
 
@@ -216,11 +217,25 @@ class Seq2RegPredictor(nn.Module):
         shift = self.expand_context.bias.float()[pos].contiguous()
         return ops.affine_rows(table, tok_label, scale, shift)
 
-    def forward(self, x, padding_mask, tissue_vector=None, context=None, only_embed=False, precision=torch.float32):
-        """x int64 [b, strands, L]; padding_mask bool [b, strands, L] (True = pad); context int64 [b] (use_context)
-        -> fp32 [b, strands, d] (reference seq2reg/model.py:193-279 with only_embed=True)."""
-        if not only_embed:
-            raise NotImplementedError("only the embedding path (only_embed=True) is part of the inference hot path")
+    def _head_operands(self):
+        """(w fp32 [T, C, F], bias fp32 [T, C], ids int32 [T] = 0 .. T-1), contiguous: tissue_classifiers[str(t)] stacked by
+        tissue id and the index list of "every tissue", the operands of ops.tissue_heads.  Weight-derived operands like every
+        other: rebuilt when a head's device, storage or in-place version changes (load_state_dict copies in place), built on the
+        main stream."""
+        heads = [self.tissue_classifiers[str(t)] for t in range(len(self.tissue_classifiers))]
+        prm = [p for h in heads for p in (h.weight, h.bias)]
+
+        def build():
+            return (torch.stack([h.weight.detach().float() for h in heads]).contiguous(),
+                    torch.stack([h.bias.detach().float() for h in heads]).contiguous(),
+                    torch.arange(len(heads), dtype=torch.int32, device=heads[0].weight.device))
+        return weights.derived(self, "_vf_stacked_heads", prm, build)
+
+    def _stacked_heads(self):
+        """(w fp32 [T, C, F], bias fp32 [T, C]) of _head_operands."""
+        return self._head_operands()[:2]
+
+    def _embed(self, x, padding_mask, context):
         b, ns, L = x.size()
         dev = self.token_embedding.weight.device
         ids = x.reshape(b * ns, L).to(dev).long().contiguous()
@@ -231,3 +246,60 @@ class Seq2RegPredictor(nn.Module):
             ctx = torch.as_tensor(context).to(dev).reshape(-1)
             ctx = ctx if torch.is_floating_point(ctx) else ctx.long().repeat_interleave(ns)
         return self.embed_packed(ids, pad, n_tokens, torch.float32, context=ctx).view(b, ns, -1)
+
+    def _check_strands(self, ns: int):
+        if self.strand_agg == "concat" and ns != 2:
+            raise ValueError(f"strand_agg='concat' heads take 2 strands (their in_features is 2 * embedding_dim), got {ns}")
+
+    def forward(self, x, padding_mask, tissue_vector=None, context=None, only_embed=False, precision=torch.float32):
+        """x int64 [b, strands, L]; padding_mask bool [b, strands, L] (True = pad); context int64 [b] (use_context)
+        -> only_embed=True: x_embed fp32 [b, strands, d];
+           only_embed=False: (logits fp32 [b, num_classes], x_embed) -- the strands aggregated (strand_agg) and every sample
+           through the classifier of ITS tissue, tissue_vector int [b] (reference seq2reg/model.py:193-302).  The encoder pass
+           is the same in both; the heads are one vf_tissue_heads launch behind it."""
+        if only_embed:
+            return self._embed(x, padding_mask, context)
+        if tissue_vector is None:
+            raise ValueError("tissue_vector is required when only_embed=False: it names the classifier head of every sample")
+        b, ns, _ = x.size()
+        self._check_strands(ns)
+        x_embed = self._embed(x, padding_mask, context)
+        tv = torch.as_tensor(tissue_vector).to(x_embed.device).long().reshape(-1).contiguous()
+        if tv.numel() != b:
+            raise ValueError(f"tissue_vector has {tv.numel()} entries for a batch of {b}")
+        w, bias = self._stacked_heads()
+        # ops.tissue_heads makes nothing: the outputs are this caller's
+        logits = torch.empty((b, w.shape[1]), dtype=torch.float32, device=x_embed.device)
+        classes = torch.empty((b,), dtype=torch.int32, device=x_embed.device)
+        with ops.scope("seq2reg"):
+            ops.tissue_heads(x_embed.view(b * ns, -1), ns, self.strand_agg, w, bias, tissue_of_row=tv, out=logits, argmax=classes)
+        return logits, x_embed
+
+    def predict_step(self, batch, batch_idx):
+        """The reference's 6-tuple (x, padding_mask, tissue_vector, y, context, _) -> logits (seq2reg/model.py:440-449)."""
+        x, padding_mask, tissue_vector, y, context, _ = batch
+        logits, _ = self.forward(x, padding_mask, tissue_vector, context if self.use_context else None)
+        return logits
+
+    def classify(self, x, padding_mask, context=None, tissues=None, probabilities=True):
+        """Every sample through the heads of every tissue in `tissues` (ids; default: all, in order): one encoder pass and one
+        vf_tissue_heads launch.  No reference counterpart (its forward takes one tissue per sample).
+        -> (fp32 [b, len(tissues), num_classes]: class probabilities, or logits with probabilities=False;
+            int32 [b, len(tissues)]: the class of the largest logit, -1 where a logit is NaN)."""
+        b, ns, _ = x.size()
+        self._check_strands(ns)
+        if tissues is not None:                     # a host list: checked here, so the wrapper needs no read-back
+            tissues = [int(t) for t in tissues]
+            for t in tissues:
+                if not 0 <= t < len(self.tissue_classifiers):
+                    raise KeyError(str(t))
+        x_embed = self._embed(x, padding_mask, context)
+        w, bias, every = self._head_operands()
+        C = bias.shape[1]
+        ids = every if tissues is None else torch.tensor(tissues, dtype=torch.int32, device=x_embed.device)
+        out = torch.empty((b, ids.numel() * C), dtype=torch.float32, device=x_embed.device)
+        classes = torch.empty((b, ids.numel()), dtype=torch.int32, device=x_embed.device)
+        with ops.scope("seq2reg"):
+            ops.tissue_heads(x_embed.view(b * ns, -1), ns, self.strand_agg, w, bias, tissues=ids, probabilities=probabilities,
+                             out=out, argmax=classes, checked=True)
+        return out.view(b, ids.numel(), C), classes
