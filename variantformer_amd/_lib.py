@@ -1,5 +1,5 @@
-"""ctypes binding of libvf_hip.so (C ABI declared in include/vf_hip.h, include/vf_hip_next.h, include/vf_hip_gene_contrib.h and
-include/vf_hip_cre_heads.h).
+"""ctypes binding of libvf_hip.so (C ABI declared in include/vf_hip.h, include/vf_hip_next.h, include/vf_hip_gene_contrib.h,
+include/vf_hip_cre_heads.h and include/vf_hip_forest.h).
 
 The product path has NO fallback: if the shared library is missing, cannot be loaded, or lacks a
 declared symbol, importing the ops raises.  Signatures are plain pointers and sizes; torch only
@@ -88,6 +88,10 @@ GENE_CONTRIB_SIGNATURES = {
 CRE_HEADS_SIGNATURES = {
     "vf_tissue_heads": [_p, _l, _i, _i, _p, _p, _i, _i, _i, _p, _p, _i, _l, _i, _p, _l, _p, _p],
 }
+# the entry declared in include/vf_hip_forest.h (decision forests on embeddings: the AD-risk predictors); bound exactly like SIGNATURES
+FOREST_SIGNATURES = {
+    "vf_forest_predict": [_p, _l, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _l, _p],
+}
 _RESTYPES = {"vf_last_error": C.c_char_p, "vf_last_kernel": C.c_char_p, "vf_bpe_create": C.c_void_p, "vf_bpe_destroy": None, "vf_bpe_encode": C.c_int64, "vf_bpe_encode_prefix": C.c_int64,
              "vf_vcf_open": C.c_void_p, "vf_vcf_close": None, "vf_vcf_num_records": C.c_int64,
              "vf_vcf_consensus": C.c_int64, "vf_build_windows": C.c_int64}
@@ -116,7 +120,7 @@ def load(path: str | None = None):
             "There is no CPU fallback for the product path.")
     lib = C.CDLL(path)
     for name, argtypes in (list(SIGNATURES.items()) + list(NEXT_SIGNATURES.items()) + list(GENE_CONTRIB_SIGNATURES.items()) +
-                           list(CRE_HEADS_SIGNATURES.items())):
+                           list(CRE_HEADS_SIGNATURES.items()) + list(FOREST_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -733,6 +733,49 @@ def tissue_heads(x: torch.Tensor, n_strands: int, strand_agg, w: torch.Tensor, b
     return out, argmax
 
 
+def forest_predict(x: torch.Tensor, bank, *, model_of_row: torch.Tensor | None = None, model: int | None = None,
+                   out: torch.Tensor, family: str = ""):
+    """A bank of decision forests on fp32 rows (vf_forest_predict, include/vf_hip_forest.h).  x fp32 [R, >= F] row-strided;
+    bank a forest.DeviceBank on x's device (forest.ForestBank.to).  Row form: model_of_row int32 [R] on the device, row r
+    through the forest model_of_row[r].  Cohort form: model, a host int, every row through that forest.  out fp32 [R, >= K],
+    row-strided; columns past K are left alone.  The caller owns every buffer and nothing is made here, as in tissue_heads.
+    A host `model` outside the bank raises IndexError; a device id outside it is not read back: the kernel reads nothing for
+    that row and writes NaN.  Returns out."""
+    b = bank
+    _dev(x, b.nodes, b.tree_root, b.leaf_values, b.base_scores, b.model_node_base, b.model_tree_base, b.model_leaf_base,
+         b.model_n_trees, model_of_row, out)
+    F, K, M = int(b.n_features), int(b.n_outputs), int(b.n_models)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= F
+    R = x.shape[0]
+    if (model_of_row is None) == (model is None):
+        raise ValueError("forest_predict takes model_of_row (one forest per row) or model (one forest for every row): "
+                         + ("not both" if model is not None else "one of them is required"))
+    if model_of_row is not None:
+        assert model_of_row.dtype == torch.int32 and model_of_row.is_contiguous() and tuple(model_of_row.shape) == (R,)
+        mid = -1
+    else:
+        mid = int(model)
+        if not 0 <= mid < M:
+            raise IndexError(f"model {mid} is not one of the bank's {M}")
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == R and out.shape[1] >= K
+    assert b.nodes.dtype == torch.int32 and b.nodes.is_contiguous() and b.leaf_values.is_contiguous()
+    post = {"identity": 0, "sigmoid": 1, "softmax": 2}[b.postprocessor]
+
+    def launch():
+        if R == 0:                                    # nothing to do (an empty tensor has no address to hand over)
+            return
+        check(_lib.load().vf_forest_predict(x.data_ptr(), x.stride(0), R, F, b.nodes.data_ptr(),
+                                            b.tree_root.data_ptr(), b.leaf_values.data_ptr(), b.base_scores.data_ptr(),
+                                            b.model_node_base.data_ptr(), b.model_tree_base.data_ptr(), b.model_leaf_base.data_ptr(),
+                                            b.model_n_trees.data_ptr(), M, K, int(b.average), post, _ptr(model_of_row), mid,
+                                            out.data_ptr(), out.stride(0), _stream()),
+              "vf_forest_predict")
+    # algorithmic bytes: the rows and the outputs once; the walks' node loads are gathers the caches serve (depth unknown here)
+    _run(launch, lambda: ("forest_predict", 0.0, 4.0 * R * (F + K), f"F={F} K={K} M={M}" + (" rows" if model_of_row is not None else ""),
+                          family or _SCOPE))
+    return out
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""
