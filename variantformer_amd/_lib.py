@@ -1,5 +1,5 @@
 """ctypes binding of libvf_hip.so (C ABI declared in include/vf_hip.h, include/vf_hip_next.h, include/vf_hip_gene_contrib.h,
-include/vf_hip_cre_heads.h and include/vf_hip_forest.h).
+include/vf_hip_cre_heads.h, include/vf_hip_forest.h and include/vf_hip_topk.h).
 
 The product path has NO fallback: if the shared library is missing, cannot be loaded, or lacks a
 declared symbol, importing the ops raises.  Signatures are plain pointers and sizes; torch only
@@ -92,6 +92,10 @@ CRE_HEADS_SIGNATURES = {
 FOREST_SIGNATURES = {
     "vf_forest_predict": [_p, _l, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _l, _p],
 }
+# the entry declared in include/vf_hip_topk.h (row-wise top-k of the attention and contribution maps); bound exactly like SIGNATURES
+TOPK_SIGNATURES = {
+    "vf_topk_rows": [_p, _l, _l, _i, _p, _i, _p, _p, _l, _p],
+}
 _RESTYPES = {"vf_last_error": C.c_char_p, "vf_last_kernel": C.c_char_p, "vf_bpe_create": C.c_void_p, "vf_bpe_destroy": None, "vf_bpe_encode": C.c_int64, "vf_bpe_encode_prefix": C.c_int64,
              "vf_vcf_open": C.c_void_p, "vf_vcf_close": None, "vf_vcf_num_records": C.c_int64,
              "vf_vcf_consensus": C.c_int64, "vf_build_windows": C.c_int64}
@@ -120,7 +124,7 @@ def load(path: str | None = None):
             "There is no CPU fallback for the product path.")
     lib = C.CDLL(path)
     for name, argtypes in (list(SIGNATURES.items()) + list(NEXT_SIGNATURES.items()) + list(GENE_CONTRIB_SIGNATURES.items()) +
-                           list(CRE_HEADS_SIGNATURES.items()) + list(FOREST_SIGNATURES.items())):
+                           list(CRE_HEADS_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + list(TOPK_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

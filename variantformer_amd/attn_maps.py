@@ -183,6 +183,18 @@ def select_layers(n_layers: int, layers=None) -> list:
     return sel
 
 
+TOP_K_MAX, TOP_K_MAX_WIDTH = 64, 16384         # VF_TOPK_MAX_K / VF_TOPK_MAX_N of include/vf_hip_topk.h
+
+
+def select_top_k(top_k=None) -> int | None:
+    """The `top_k` a request names: None (the full maps) or an int in 1 .. 64; ValueError otherwise (a bool or a float too)."""
+    if top_k is None:
+        return None
+    if isinstance(top_k, bool) or not hasattr(top_k, "__index__") or not 1 <= int(top_k) <= TOP_K_MAX:
+        raise ValueError(f"attention maps: top_k must be None or an int in 1 .. {TOP_K_MAX}, got {top_k!r}")
+    return int(top_k)
+
+
 def active() -> Capture | None:
     """The capture open in this context, or None."""
     return _CAP.get()

@@ -52,12 +52,13 @@ class KernelTimer:
     def __init__(self, detail: bool = False):
         self.records = {}
         self.detail = detail          # also key records by launch geometry (scripts/shape_breakdown.py)
-        self.order = []               # (name, geometry, family, flops | None, bytes) of every launch, in launch order
+        self.order = []               # (name, geometry, family, flops | None, bytes | None) of every launch, in launch order
                                       # (scripts/pmc_shapes.py joins it with the dispatch order of a rocprofv3 counter pass)
 
     def time(self, name: str, flops, nbytes: float, launch, geometry: str = "", family: str = ""):
         """flops: a number, or a zero-argument callable evaluated in summary() (attention: the per-sequence lengths
-        live on the device, and reading them here would put a host sync between the launches being timed)."""
+        live on the device, and reading them here would put a host sync between the launches being timed).  nbytes: the
+        same (topk_rows: the rows' lengths live on the device)."""
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         out = launch()
@@ -65,7 +66,8 @@ class KernelTimer:
         rec = [a, b, flops, nbytes]
         self.records.setdefault(name, []).append(rec)
         if self.detail:
-            self.order.append((name, geometry, family, None if callable(flops) else float(flops), float(nbytes)))
+            self.order.append((name, geometry, family, None if callable(flops) else float(flops),
+                               None if callable(nbytes) else float(nbytes)))
         if family:
             self.records.setdefault(f"{name}:{family}", []).append(rec)
         if self.detail and geometry:
@@ -79,6 +81,8 @@ class KernelTimer:
             for r in recs:
                 if callable(r[2]):
                     r[2] = float(r[2]())
+                if callable(r[3]):
+                    r[3] = float(r[3]())
             ms = sum(a.elapsed_time(b) for a, b, _, _ in recs)
             out[name] = {"launches": len(recs), "total_ms": ms, "flops": sum(r[2] for r in recs),
                          "bytes": sum(r[3] for r in recs)}
@@ -774,6 +778,38 @@ def forest_predict(x: torch.Tensor, bank, *, model_of_row: torch.Tensor | None =
     _run(launch, lambda: ("forest_predict", 0.0, 4.0 * R * (F + K), f"F={F} K={K} M={M}" + (" rows" if model_of_row is not None else ""),
                           family or _SCOPE))
     return out
+
+
+def topk_rows(x: torch.Tensor, k: int, *, row_len: torch.Tensor | None = None, values: torch.Tensor, indices: torch.Tensor,
+              family: str = ""):
+    """The k first-ranked values of every row and their columns (vf_topk_rows, include/vf_hip_topk.h).  x fp32 [R, n]
+    row-strided, n <= 16384, k in 1 .. 64; row_len int32 [R] on the device (None: every row has n columns): columns at or past
+    it are never read.  NaNs rank first, then descending by IEEE comparison; ties (+0 / -0, all NaNs) go to the lower column.
+    values fp32 [R, >= k] and indices int32 [R, >= k], both row-strided with ONE row stride; columns past k are left alone;
+    ranks a row has no column for are -1 / +0.0.  The caller owns every buffer and nothing is made here, as in forest_predict.
+    Returns (values, indices)."""
+    _dev(x, row_len, values, indices)
+    k = int(k)
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    R, n = x.shape
+    assert row_len is None or (row_len.dtype == torch.int32 and row_len.is_contiguous() and tuple(row_len.shape) == (R,))
+    assert values.dtype == torch.float32 and values.dim() == 2 and values.stride(1) == 1 and values.shape[0] == R and values.shape[1] >= k
+    assert indices.dtype == torch.int32 and indices.dim() == 2 and indices.stride(1) == 1 and indices.shape[0] == R and indices.shape[1] >= k
+    assert R <= 1 or values.stride(0) == indices.stride(0), "values and indices share one row stride"
+    ldx = x.stride(0) if R > 1 else max(x.stride(0), n)
+    ldo = values.stride(0) if R > 1 else max(values.stride(0), k)
+
+    def launch():
+        if R == 0:                                    # nothing to do (an empty tensor has no address to hand over)
+            return
+        # n == 0: every rank is padding, nothing is read, and an empty tensor has no address: `values` stands in for it
+        check(_lib.load().vf_topk_rows(x.data_ptr() if n else values.data_ptr(), ldx, R, n, _ptr(row_len), k, values.data_ptr(),
+                                       indices.data_ptr(), ldo, _stream()), "vf_topk_rows")
+    # algorithmic bytes: the rows' valid values once and the outputs (the lengths live on the device: summed in summary())
+    _run(launch, lambda: ("topk_rows", 0.0,
+                          (lambda: 4.0 * (float(row_len.clamp(0, n).sum()) + 2.0 * R * k)) if row_len is not None else 4.0 * R * (n + 2 * k),
+                          f"n={n} k={k}" + (" ragged" if row_len is not None else ""), family or _SCOPE))
+    return values, indices
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,

@@ -12,6 +12,7 @@ import gzip
 import os
 from pathlib import Path
 
+import numpy as np
 import pandas as pd
 import torch
 import yaml
@@ -143,7 +144,7 @@ class VCFProcessor:
         return self.format_output(vcf_dataset.query_df, predictions)
 
     def predict_with_attention(self, model, checkpoint_path, trainer, dataloader, vcf_dataset, layers=None, per_head=False,
-                               gene_body=False, contributions=False, gene_contributions=False):
+                               gene_body=False, contributions=False, gene_contributions=False, top_k=None):
         """`predict`'s frame plus the gene -> cCRE attention maps of the same forwards (no reference counterpart: flash-attn
         returns no probabilities).  New columns, one entry per gene:
           cre_attention         fp32 [len(layers), tissues, cCREs] (per_head: [len(layers), tissues, heads, cCREs]) -- how much the
@@ -167,7 +168,15 @@ class VCFProcessor:
           gene_contribution     fp32, shaped and ordered like gene_attention -- the same norm through the SELF attention's output
                                 projection: column 0 is what the registry token's own value adds, column 1 + c what gene-body
                                 chunk c (gene_chunk_table) adds; the quantity to rank chunks by, comparable with cre_contribution.
-        A plain loop over the loader (the maps are read back per batch)."""
+        top_k=K (1 .. 64) returns rankings instead of maps: the selection runs on the device behind each forward and only K
+        values and K indices per row are read back.  In place of every map column above the frame holds
+          <name>_top_value      fp32 [len(layers), tissues, K] (per_head: [len(layers), tissues, heads, K]) -- the K largest
+                                entries of each row of the map, descending;
+          <name>_top_index      int32, the same shape -- their columns in the full map (a row of cre_names / 1 + a row of
+                                gene_chunk_table; 0 in a gene-body map is the token itself), -1 where the gene has fewer than K;
+          cre_attention_top_names, cre_contribution_top_names   the cre_name of every index (None for -1), where the dataset
+                                has cre_table.
+        A plain loop over the loader (the maps or the rankings are read back per batch)."""
         model.trainer = trainer
         model.eval()
         kw = {"gene_body": True} if gene_body else {}
@@ -175,6 +184,8 @@ class VCFProcessor:
             kw["contributions"] = True
         if gene_contributions:
             kw["gene_contributions"] = True
+        if top_k is not None:
+            kw["top_k"] = top_k
         predictions = [model.predict_step_with_attention(batch, i, layers=layers, per_head=per_head, **kw)
                        for i, batch in enumerate(dataloader)]
         try:       # as Trainer.predict: what the self-healing LayerNorm fold did during this pass
@@ -183,28 +194,44 @@ class VCFProcessor:
         except Exception:                                     # a model class without the fold
             trainer.ln_fold_state = None
         df = self.format_output(vcf_dataset.query_df, predictions)
-        maps = [m for p in predictions for m in p["cre_attention"]]
-        df["cre_attention"] = pd.Series(maps, index=df.index, dtype=object)
-        df["cre_attention_layers"] = pd.Series([list(p["cre_attention_layers"]) for p in predictions for _ in p["cre_attention"]],
+        suffixes = ("",) if top_k is None else ("_top_value", "_top_index")
+
+        def column(key):
+            for sfx in suffixes:
+                df[key + sfx] = pd.Series([m for p in predictions for m in p[key + sfx]], index=df.index, dtype=object)
+
+        def widths(kind):                                            # the gene's columns in the full map, from the prediction
+            if top_k is not None:
+                return [w for p in predictions for w in p[kind + "_map_width"]]
+            key = {"cre": "cre_attention", "gene": "gene_attention" if gene_body else "gene_contribution"}[kind]
+            return [m.shape[-1] for p in predictions for m in p[key]]
+        column("cre_attention")
+        df["cre_attention_layers"] = pd.Series([list(p["cre_attention_layers"]) for p in predictions for _ in p["pred_gene_exp"]],
                                                index=df.index, dtype=object)
         if hasattr(vcf_dataset, "cre_table"):
             tables = [vcf_dataset.cre_table(g) for g in df["gene_id"]]
-            for g, t, m in zip(df["gene_id"], tables, maps):         # a name per map column, or no names at all
-                assert len(t) == m.shape[-1], f"{g}: cre_table names {len(t)} windows, the map has {m.shape[-1]} columns"
+            for g, t, w in zip(df["gene_id"], tables, widths("cre")):     # a name per map column, or no names at all
+                assert len(t) == w, f"{g}: cre_table names {len(t)} windows, the map has {w} columns"
             for col, src in (("cre_names", "cre_name"), ("cre_start", "start_cre"), ("cre_end", "end_cre")):
                 df[col] = pd.Series([t[src].tolist() for t in tables], index=df.index, dtype=object)
+            if top_k is not None:
+                for key in ("cre_attention",) + (("cre_contribution",) if contributions else ()):
+                    idx = [m for p in predictions for m in p[key + "_top_index"]]
+                    names = []
+                    for t, ix in zip(tables, idx):
+                        lut = np.array(t["cre_name"].tolist() + [None], dtype=object)       # -1 finds the None at the end
+                        names.append(lut[ix])
+                    df[key + "_top_names"] = pd.Series(names, index=df.index, dtype=object)
         if contributions:
-            df["cre_contribution"] = pd.Series([m for p in predictions for m in p["cre_contribution"]], index=df.index, dtype=object)
+            column("cre_contribution")
         if gene_body or gene_contributions:
-            gmaps = []
             for key, on in (("gene_attention", gene_body), ("gene_contribution", gene_contributions)):
                 if on:
-                    gmaps = [m for p in predictions for m in p[key]]
-                    df[key] = pd.Series(gmaps, index=df.index, dtype=object)
+                    column(key)
             if hasattr(vcf_dataset, "gene_chunk_table"):
                 tables = [vcf_dataset.gene_chunk_table(g) for g in df["gene_id"]]
-                for g, t, m in zip(df["gene_id"], tables, gmaps):    # a row per map column behind the registry token's
-                    assert len(t) == m.shape[-1] - 1, f"{g}: gene_chunk_table has {len(t)} chunks, the map {m.shape[-1] - 1}"
+                for g, t, w in zip(df["gene_id"], tables, widths("gene")):    # a row per map column behind the registry token's
+                    assert len(t) == w - 1, f"{g}: gene_chunk_table has {len(t)} chunks, the map {w - 1}"
                 for col, src in (("gene_chunk_seq_start", "seq_start"), ("gene_chunk_seq_end", "seq_end"),
                                  ("gene_chunk_start", "start"), ("gene_chunk_end", "end")):
                     df[col] = pd.Series([[None if pd.isna(v) else int(v) for v in t[src]] for t in tables], index=df.index,

@@ -966,7 +966,7 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
                                       "evaluation order of the options the shipped configuration leaves off)")
 
     def predict_step_with_attention(self, batch, batch_idx, dataloader_idx=None, layers=None, per_head=False, gene_body=False,
-                                    contributions=False, gene_contributions=False):
+                                    contributions=False, gene_contributions=False, top_k=None):
         """predict_step's dict plus the attention maps of the registry tokens in the same forward:
           "cre_attention"         per gene, fp32 numpy [len(layers), T_i, N_i] -- the head mean of the softmax of gene layer
                                   `layers[k]`'s cross attention on the registry-token row of tissue t (tissues in the order of
@@ -989,30 +989,47 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
         layers: distinct gene-layer indices (negative: from the end; None: all; ValueError for an index out of range, an empty
         list or a layer named twice).  When the batch trips the LayerNorm-fold alert the
         recomputation runs under the capture too and the maps are its maps.  A vep model has
-        variant_prediction_with_attention instead (variant_prediction's dict plus the same maps)."""
+        variant_prediction_with_attention instead (variant_prediction's dict plus the same maps).
+        top_k: None, or K in 1 .. 64 (ValueError otherwise): the ranking instead of the maps.  The forward and the capture run
+        as without it; every requested map is then ranked per row on the device (ops.topk_rows) and only the selections are
+        copied to the host.  The four full-map keys above are absent; for each requested map the dict holds
+          "<name>_top_value"      per gene, fp32 numpy [len(layers), T_i, K] ([len(layers), T_i, H, K] with per_head): the K
+                                  largest entries of the map's row, descending (a NaN first; ties to the lower column);
+          "<name>_top_index"      int32, the same shape: their columns in the full map -- cCRE j in the order of
+                                  cre_sequences[i]; for the gene-body maps 0 the token itself and 1 + c chunk c -- and -1
+                                  (value 0.0) past the gene's last column where it has fewer than K;
+          "cre_map_width"         per gene, N_i: how many columns the ranked cCRE maps had ("gene_map_width": 1 + C_i, with
+                                  gene_body or gene_contributions).
+        A map wider than 16384 columns raises ValueError."""
         self.eval()
         self._attention_maps_supported()
         sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
+        top_k = attn_maps.select_top_k(top_k)
         with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions, gene_contributions) as cap:
             out = self.predict_finish(self.predict_launch(self.prepare_batch(batch)), batch_idx, dataloader_idx)
-            return self._with_attention(out, cap)         # the recomputation's maps when predict_finish healed the batch
+            return self._with_attention(out, cap, top_k)  # the recomputation's maps when predict_finish healed the batch
 
     def variant_prediction_with_attention(self, batch, layers=None, per_head=False, gene_body=False, contributions=False,
-                                          gene_contributions=False):
+                                          gene_contributions=False, top_k=None):
         """variant_prediction's dict (bit for bit) plus "cre_attention", "cre_attention_layers" and, with gene_body /
         contributions / gene_contributions, "gene_attention" / "cre_contribution" / "gene_contribution" as
         predict_step_with_attention describes them, with one entry per
         genotype of the batch, in batch order: ref, het, hom -- how a variant moved the model's attention.  The VEP forward keeps the full last gene layer (it
         reads token-position rows of it), so every layer records through the row map of the registry rows.  When the batch
-        trips the LayerNorm-fold alert the recomputation runs under the capture too and the maps are its maps."""
+        trips the LayerNorm-fold alert the recomputation runs under the capture too and the maps are its maps.
+        top_k: as in predict_step_with_attention, one "<name>_top_value" / "<name>_top_index" entry per genotype."""
         self.eval()
         self._attention_maps_supported(vep_ok=True)
         sel = attn_maps.select_layers(len(self.combined_modulator.gene_layers), layers)
+        top_k = attn_maps.select_top_k(top_k)
         with torch.no_grad(), attn_maps.capture(sel, per_head, gene_body, contributions, gene_contributions) as cap:
-            return self._with_attention(self.variant_prediction(batch), cap)
+            return self._with_attention(self.variant_prediction(batch), cap, top_k)
 
-    def _with_attention(self, out: dict, cap) -> dict:
-        """`out` plus the maps of the capture's most recent forward (call inside the capture block), split per gene."""
+    def _with_attention(self, out: dict, cap, top_k=None) -> dict:
+        """`out` plus the maps of the capture's most recent forward (call inside the capture block), split per gene; with
+        top_k their rankings instead (_with_top_k)."""
+        if top_k is not None:
+            return self._with_top_k(out, cap, top_k)
         sel, per_head = list(cap.layers), cap.per_head
         H = self.combined_modulator.num_heads
 
@@ -1036,6 +1053,57 @@ class Seq2GenePredictorCombinedModulator(nn.Module):
             out["cre_contribution"] = per_gene(cap.contrib, cap.shape[1] if cap.shape else [])
         if cap.gene_contributions:
             out["gene_contribution"] = per_gene(cap.gene_contrib, [1 + c for c in cap.shape[2]] if cap.shape else [])
+        return out
+
+    def _with_top_k(self, out: dict, cap, top_k: int) -> dict:
+        """`out` plus, for every map the capture holds, the top_k first-ranked entries of each row and their columns, split per
+        gene: each buffer [L, rows, max_k] is ranked as [L * rows, max_k] by one ops.topk_rows call behind the forward, with
+        the gene's own width as the row's length (the padding columns are never read), and only the selections are copied."""
+        sel, per_head = list(cap.layers), cap.per_head
+        H = self.combined_modulator.num_heads
+        rep = H if per_head else 1
+        tissues = list(cap.shape[0]) if cap.shape else []
+        row_len = {}                                      # "cre" / "gene" -> int32 [L * rows] on the device, once per forward
+
+        def lengths(kind, device):
+            if kind not in row_len:
+                widths = cap.shape[1] if kind == "cre" else [1 + c for c in cap.shape[2]]
+                per_row = [int(w) for t, w in zip(tissues, widths) for _ in range(t * rep)]
+                row_len[kind] = torch.tensor(per_row * len(sel), dtype=torch.int32).to(device)
+            return row_len[kind]
+
+        def ranked(name, m, kind):
+            if m is None:                                 # no forward ran: an empty batch
+                out[name + "_top_value"], out[name + "_top_index"] = [], []
+                return
+            if m.shape[-1] > attn_maps.TOP_K_MAX_WIDTH:
+                raise ValueError(f"attention maps: top_k ranks maps of at most {attn_maps.TOP_K_MAX_WIDTH} columns, "
+                                 f"{name} has {m.shape[-1]}")
+            rows = m.shape[0] * m.shape[1]
+            assert m.is_contiguous() and m.shape[0] == len(sel) and m.shape[1] == sum(tissues) * rep
+            values = torch.empty((rows, top_k), dtype=torch.float32, device=m.device)
+            indices = torch.empty((rows, top_k), dtype=torch.int32, device=m.device)
+            ops.topk_rows(m.view(rows, m.shape[-1]), top_k, row_len=lengths(kind, m.device), values=values, indices=indices,
+                          family=name + "_topk")
+            for suffix, buf in (("_top_value", values), ("_top_index", indices)):
+                a = buf.cpu().numpy().reshape(len(sel), m.shape[1], top_k)
+                res, r = [], 0
+                for t in tissues:
+                    g = np.ascontiguousarray(a[:, r * rep:(r + t) * rep])
+                    res.append(g.reshape(len(sel), t, H, top_k) if per_head else g)
+                    r += t
+                out[name + suffix] = res
+        ranked("cre_attention", cap.maps, "cre")
+        out["cre_attention_layers"] = sel
+        out["cre_map_width"] = [int(w) for w in cap.shape[1]] if cap.shape else []        # what an index counts up to, per gene
+        if cap.gene_body or cap.gene_contributions:
+            out["gene_map_width"] = [1 + int(c) for c in cap.shape[2]] if cap.shape else []
+        if cap.gene_body:
+            ranked("gene_attention", cap.gene_maps, "gene")
+        if cap.contributions:
+            ranked("cre_contribution", cap.contrib, "cre")
+        if cap.gene_contributions:
+            ranked("gene_contribution", cap.gene_contrib, "gene")
         return out
 
     def predict_launch(self, pb: PreparedBatch) -> PredictHandle:
