@@ -812,6 +812,83 @@ def topk_rows(x: torch.Tensor, k: int, *, row_len: torch.Tensor | None = None, v
     return values, indices
 
 
+def _rows(t: torch.Tensor, width: int, name: str):
+    """(row count, row stride in elements) of a row-strided fp32 / int32 matrix that holds at least `width` columns."""
+    assert t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] <= 1) and t.shape[1] >= width, f"{name}: a [rows, >= {width}] matrix with unit column stride"
+    return t.shape[0], (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1], width, 1))
+
+
+def rows_standardize(x: torch.Tensor, *, center: bool = True, z: torch.Tensor, norm: torch.Tensor | None = None, family: str = ""):
+    """Rows to zero mean (center) and unit norm (vf_rows_standardize, include/vf_hip_neighbors.h): after it a dot product of two
+    rows is their Pearson correlation (center=True) or cosine.  x fp32 [R, d] row-strided; z fp32 [R, d] row-strided (z may be
+    x); norm None or fp32 [R] contiguous.  Two-pass fp32; a row with norm 0 becomes +0.0 with norm 0, a row with a NaN or an
+    Inf becomes NaN with norm NaN.  The caller owns every buffer and nothing is made here.  Returns (z, norm)."""
+    _dev(x, z, norm)
+    assert x.dtype == torch.float32 and z.dtype == torch.float32 and x.dim() == 2 and x.shape[1] >= 1
+    d = x.shape[1]
+    R, ldx = _rows(x, d, "x")
+    Rz, ldz = _rows(z, d, "z")
+    assert Rz == R and z.shape[1] == d, "z has x's shape"
+    assert norm is None or (norm.dtype == torch.float32 and norm.is_contiguous() and tuple(norm.shape) == (R,))
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_rows_standardize(x.data_ptr(), ldx, R, d, int(bool(center)), z.data_ptr(), ldz, _ptr(norm), _stream()),
+              "vf_rows_standardize")
+    _run(launch, lambda: ("rows_standardize", 4.0 * R * d, 4.0 * R * (2 * d + 1), f"d={d}", family or _SCOPE))
+    return z, norm
+
+
+def knn_dot(q: torch.Tensor, y: torch.Tensor, k: int, *, self_offset: int = -1, values: torch.Tensor, indices: torch.Tensor,
+            family: str = ""):
+    """For every row of q the k rows of y with the largest dot product (vf_knn_dot, include/vf_hip_neighbors.h), formed tile by
+    tile on the f32 MFMA: no [Rq, Ry] buffer exists.  q fp32 [Rq, d] and y fp32 [Ry, d] row-strided; self_offset -1, or the
+    row of y at which q starts as a slice of it (row r then skips y[r + self_offset]).  The order is topk_rows's: NaN first,
+    descending, ties to the lower row.  values fp32 [Rq, >= k] and indices int32 [Rq, >= k] with ONE row stride; columns past
+    k are left alone; ranks a row has no candidate for are -1 / +0.0.  The caller owns every buffer.  Returns (values, indices)."""
+    _dev(q, y, values, indices)
+    k = int(k)
+    assert q.dtype == torch.float32 and y.dtype == torch.float32 and q.dim() == 2 and y.dim() == 2 and q.shape[1] == y.shape[1] >= 1
+    d = q.shape[1]
+    Rq, ldq = _rows(q, d, "q")
+    Ry, ldy = _rows(y, d, "y")
+    assert values.dtype == torch.float32 and indices.dtype == torch.int32
+    Rv, ldo = _rows(values, k, "values")
+    Ri, ldi = _rows(indices, k, "indices")
+    assert Rv == Ri == Rq and (Rq <= 1 or ldo == ldi), "values and indices have Rq rows and share one row stride"
+
+    def launch():
+        if Rq == 0:
+            return
+        # Ry == 0: every rank is padding, nothing is read, and an empty tensor has no address: `q` stands in for it
+        check(_lib.load().vf_knn_dot(q.data_ptr(), ldq, Rq, y.data_ptr() if Ry else q.data_ptr(), ldy, Ry, d, int(self_offset), k,
+                                     values.data_ptr(), indices.data_ptr(), ldo, _stream()), "vf_knn_dot")
+    _run(launch, lambda: ("knn_dot", 2.0 * Rq * Ry * d, 4.0 * (Rq * d + Ry * d + 2 * Rq * k), f"Ry={Ry} d={d} k={k}", family or _SCOPE))
+    return values, indices
+
+
+def pairwise_dot(q: torch.Tensor, y: torch.Tensor, *, mode: int = 0, self_offset: int = -1, out: torch.Tensor, family: str = ""):
+    """out[r, j] = the dot product of q[r] and y[j] (mode 0), bit for bit what knn_dot ranks, or 1 - it with exactly 0 at
+    j == r + self_offset (mode 1: 1 - corrcoef with a zero diagonal, on standardised rows).  vf_pairwise_dot,
+    include/vf_hip_neighbors.h.  q fp32 [Rq, d], y fp32 [Ry, d], out fp32 [Rq, Ry], all row-strided; the caller owns out."""
+    _dev(q, y, out)
+    assert q.dtype == torch.float32 and y.dtype == torch.float32 and q.dim() == 2 and y.dim() == 2 and q.shape[1] == y.shape[1] >= 1
+    d = q.shape[1]
+    Rq, ldq = _rows(q, d, "q")
+    Ry, ldy = _rows(y, d, "y")
+    assert out.dtype == torch.float32 and out.dim() == 2 and tuple(out.shape) == (Rq, Ry)
+    ldo = _rows(out, Ry, "out")[1]
+
+    def launch():
+        if Rq == 0 or Ry == 0:
+            return
+        check(_lib.load().vf_pairwise_dot(q.data_ptr(), ldq, Rq, y.data_ptr(), ldy, Ry, d, int(self_offset), int(mode), out.data_ptr(),
+                                          ldo, _stream()), "vf_pairwise_dot")
+    _run(launch, lambda: ("pairwise_dot", 2.0 * Rq * Ry * d, 4.0 * (Rq * d + Ry * d + Rq * Ry), f"Ry={Ry} d={d} mode={int(mode)}", family or _SCOPE))
+    return out
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

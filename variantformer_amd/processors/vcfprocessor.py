@@ -280,6 +280,39 @@ class VCFProcessor:
                 df[col] = pd.Series([t[src].tolist() for t in tables], index=df.index, dtype=object)
         return df
 
+    def expression_neighbors(self, df, k: int = 30, on: str = "predicted_expression", axis: str = "genes", tissue=None,
+                             metric: str = "correlation"):
+        """The correlation k-nearest neighbours among the rows of a finished prediction: `df` is what
+        format_output returned; the matrix is neighbors.from_predictions(df, on, axis, tissue) and the search runs on the
+        device (neighbors.knn: rows standardised in fp32, similarities on the f32 MFMA, no rows x rows buffer).  No model and
+        no checkpoint are involved.  Per row of the matrix:
+          neighbor_ids         the labels of its k nearest rows, nearest first (None where the matrix has fewer than k others);
+          neighbor_distance    fp32 [k], 1 - correlation, ascending (+Inf beside a None);
+          neighbor_degenerate  True for a row without variation (its norm is 0): it is at distance 1 from everything.
+        Rows that are genes (axis="genes" with expression, or embeddings of one `tissue`) get these as three columns of `df`,
+        which is returned.  Embeddings with tissue=None have (gene, tissue) rows: each gene's cell then holds its tissues'
+        results, [tissues, k] / [tissues].  axis="tissues" has no gene rows: a new frame is returned, one row per tissue
+        under the column `tissue`."""
+        from .. import neighbors
+        m, labels = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
+        idx, dist, norm = neighbors._knn(m, k, metric, None, False, False)
+        idx, dist, flat = idx.cpu().numpy(), dist.cpu().numpy(), (norm == 0).cpu().numpy()
+        lut = np.empty(len(labels) + 1, dtype=object)                    # -1 finds the None at the end
+        for i, label in enumerate(labels):                               # one by one: a (gene, tissue) label stays one object
+            lut[i] = label
+        lut[len(labels)] = None
+        ids = lut[idx]
+        if axis == "tissues":
+            return pd.DataFrame({"tissue": labels, "neighbor_ids": list(ids), "neighbor_distance": list(dist),
+                                 "neighbor_degenerate": flat})
+        per = len(labels) // len(df)                                     # 1, or the tissues of a (gene, tissue) row set
+        if per > 1:
+            ids, dist, flat = ids.reshape(len(df), per, -1), dist.reshape(len(df), per, -1), flat.reshape(len(df), per)
+        df["neighbor_ids"] = pd.Series(list(ids), index=df.index, dtype=object)
+        df["neighbor_distance"] = pd.Series(list(dist), index=df.index, dtype=object)
+        df["neighbor_degenerate"] = pd.Series(list(flat), index=df.index, dtype=object if per > 1 else bool)
+        return df
+
     def predict_distributed(self, model, checkpoint_path, trainer, vcf_dataset, batch_size: int | None = None, costs=None,
                             **loader_kwargs):
         """Multi-GPU vcf2exp (the reference is single-device, vcfprocessor.py:252-258): call from every rank
