@@ -889,6 +889,66 @@ def pairwise_dot(q: torch.Tensor, y: torch.Tensor, *, mode: int = 0, self_offset
     return out
 
 
+def _square(t: torch.Tensor, name: str):
+    """(side, row stride in elements) of a row-strided fp32 square matrix."""
+    assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == t.shape[1], f"{name}: a square fp32 matrix"
+    return _rows(t, t.shape[0], name)
+
+
+def _vec(t: torch.Tensor, n: int, dtype, name: str):
+    assert t.dtype == dtype and t.dim() == 1 and t.shape[0] == n and (n <= 1 or t.stride(0) == 1), f"{name}: a contiguous {dtype} [{n}]"
+
+
+def linkage_nearest(D: torch.Tensor, *, nn_val: torch.Tensor, nn_idx: torch.Tensor, family: str = ""):
+    """For every row i of the square matrix D its smallest D[i, j], j != i, and that j (vf_linkage_nearest,
+    include/vf_hip_linkage.h).  D fp32 [m, m] row-strided, only read; nn_val fp32 [m] and nn_idx int32 [m] contiguous.  Ascending
+    by IEEE comparison, NaN last (above +Inf), +0 and -0 tie, ties to the lower j; m == 1 gives -1 / +Inf.  The caller owns
+    every buffer and nothing is made here.  Returns (nn_val, nn_idx)."""
+    _dev(D, nn_val, nn_idx)
+    m, ld = _square(D, "D")
+    _vec(nn_val, m, torch.float32, "nn_val")
+    _vec(nn_idx, m, torch.int32, "nn_idx")
+
+    def launch():
+        if m == 0:
+            return
+        check(_lib.load().vf_linkage_nearest(D.data_ptr(), ld, m, nn_val.data_ptr(), nn_idx.data_ptr(), _stream()), "vf_linkage_nearest")
+    _run(launch, lambda: ("linkage_nearest", 0.0, 4.0 * (m * m + 2 * m), f"m={m}", family or _SCOPE))
+    return nn_val, nn_idx
+
+
+def linkage_contract(D: torch.Tensor, size: torch.Tensor, first: torch.Tensor, second: torch.Tensor, *, upper_only: bool = False,
+                     out: torch.Tensor, size_out: torch.Tensor, pair_dist: torch.Tensor, family: str = ""):
+    """One round of Ward merges (vf_linkage_contract, include/vf_hip_linkage.h): new cluster a is old cluster first[a] alone
+    (second[a] == -1) or the merge of first[a] < second[a]; out [m_out, m_out] gets the Lance-Williams distances between the new
+    clusters (symmetric bit for bit, diagonal +0), size_out [m_out] their sizes and pair_dist [m_out] each merged pair's own
+    distance (+0 for a cluster that stands alone).  D fp32 [m, m] row-strided and size int32 [m] are only read; first and second
+    int32 [m_out], first strictly increasing, constituents disjoint (not checked).  upper_only: read D's upper triangle alone
+    (the first round, on the caller's matrix).  out must not overlap D.  The caller owns every buffer and nothing is made here.
+    Returns (out, size_out, pair_dist)."""
+    _dev(D, size, first, second, out, size_out, pair_dist)
+    m, ld = _square(D, "D")
+    m_out, ld_out = _square(out, "out")
+    assert m_out <= m
+    _vec(size, m, torch.int32, "size")
+    _vec(first, m_out, torch.int32, "first")
+    _vec(second, m_out, torch.int32, "second")
+    _vec(size_out, m_out, torch.int32, "size_out")
+    _vec(pair_dist, m_out, torch.float32, "pair_dist")
+
+    def launch():
+        if m_out == 0:
+            return
+        check(_lib.load().vf_linkage_contract(D.data_ptr(), ld, m, size.data_ptr(), first.data_ptr(), second.data_ptr(), m_out,
+                                              out.data_ptr(), ld_out, size_out.data_ptr(), pair_dist.data_ptr(), int(bool(upper_only)),
+                                              _stream()), "vf_linkage_contract")
+    # algorithmic bytes: every old row once (it belongs to one new slot), the output, the per-slot vectors; operations: one
+    # Lance-Williams update of about 12 per element (none where both slots stand alone, three where both are pairs)
+    _run(launch, lambda: ("linkage_contract", 12.0 * m_out * m_out, 4.0 * (m * m + m_out * m_out + 6 * m_out), f"m={m} m_out={m_out}",
+                          family or _SCOPE))
+    return out, size_out, pair_dist
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

@@ -313,6 +313,21 @@ class VCFProcessor:
         df["neighbor_degenerate"] = pd.Series(list(flat), index=df.index, dtype=object if per > 1 else bool)
         return df
 
+    def expression_dendrogram(self, df, on: str = "predicted_expression", axis: str = "tissues", tissue=None):
+        """The Ward tree over the rows of a finished prediction, what vcf2exp's compute_ordered_leaves
+        computes with scipy: `df` is what format_output returned; the matrix is neighbors.from_predictions(df, on, axis, tissue),
+        its correlation distances and their linkage are formed on the device (linkage.ward_of_rows).  axis="tissues" is the
+        notebook's tissue dendrogram, axis="genes" the row order of its heatmap.  No model and no checkpoint are involved.
+        Returns a dict:
+          Z               float64 [rows - 1, 4], scipy's linkage format (scipy.cluster.hierarchy.dendrogram takes it);
+          leaves          int32 [rows], the rows from left to right;
+          labels          what names each row of the matrix;  ordered_labels  the labels in `leaves` order."""
+        from .. import linkage, neighbors
+        m, labels = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
+        Z = linkage.ward_of_rows(m)
+        leaves = linkage.leaves_list(Z)
+        return {"Z": Z, "leaves": leaves, "labels": labels, "ordered_labels": [labels[i] for i in leaves]}
+
     def predict_distributed(self, model, checkpoint_path, trainer, vcf_dataset, batch_size: int | None = None, costs=None,
                             **loader_kwargs):
         """Multi-GPU vcf2exp (the reference is single-device, vcfprocessor.py:252-258): call from every rank
