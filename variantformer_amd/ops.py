@@ -949,6 +949,97 @@ def linkage_contract(D: torch.Tensor, size: torch.Tensor, first: torch.Tensor, s
     return out, size_out, pair_dist
 
 
+def umap_smooth_knn(idx: torch.Tensor, dist: torch.Tensor, mean_dist: float, *, rho: torch.Tensor, sigma: torch.Tensor,
+                    strength: torch.Tensor, family: str = ""):
+    """rho, sigma and the directed membership strengths of every row's neighbour list (vf_umap_smooth_knn,
+    include/vf_hip_umap.h): umap-learn's smooth_knn_dist (local_connectivity 1) and compute_membership_strengths.  idx int32
+    [R, m] and dist fp32 [R, m] row-strided, the others-only lists of neighbors.knn, only read; m in 1 .. 63; an entry with a
+    negative index or a NaN / infinite distance is absent.  mean_dist: the mean of the present distances.  rho, sigma fp32 [R]
+    contiguous; strength fp32 [R, m] row-strided.  The caller owns every buffer and nothing is made here.  Returns
+    (rho, sigma, strength)."""
+    _dev(idx, dist, rho, sigma, strength)
+    assert idx.dtype == torch.int32 and dist.dtype == torch.float32 and strength.dtype == torch.float32 and idx.dim() == 2
+    m = idx.shape[1]
+    assert 1 <= m <= 63, f"m={m} outside 1 .. 63"
+    R, ld_idx = _rows(idx, m, "idx")
+    assert dist.shape == idx.shape and strength.shape == idx.shape
+    _, ld_dist = _rows(dist, m, "dist")
+    _, ld_strength = _rows(strength, m, "strength")
+    _vec(rho, R, torch.float32, "rho")
+    _vec(sigma, R, torch.float32, "sigma")
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_umap_smooth_knn(idx.data_ptr(), ld_idx, dist.data_ptr(), ld_dist, R, m, float(mean_dist), rho.data_ptr(),
+                                             sigma.data_ptr(), strength.data_ptr(), ld_strength, _stream()), "vf_umap_smooth_knn")
+    # operations: up to 64 bisection steps of one exp per entry; bytes: the two lists in, strengths and two vectors out
+    _run(launch, lambda: ("umap_smooth_knn", 65.0 * 4 * R * m, 4.0 * (3 * R * m + 2 * R), f"R={R} m={m}", family or _SCOPE))
+    return rho, sigma, strength
+
+
+def umap_union(idx: torch.Tensor, strength: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, *, w: torch.Tensor, family: str = ""):
+    """The fuzzy union of the directed strengths over the symmetric graph (vf_umap_union, include/vf_hip_umap.h): for every CSR
+    entry (i, j = col[e]) w[e] = (a + b) - a * b with a the strength of j in row i's list and b that of i in row j's, +0 where
+    it is not listed; w[i -> j] and w[j -> i] have the same bits.  idx int32 [R, m] and strength fp32 [R, m] row-strided;
+    rowptr int64 [R + 1], col int32 [nnz], w fp32 [nnz] contiguous.  The caller owns every buffer and nothing is made here.
+    Returns w."""
+    _dev(idx, strength, rowptr, col, w)
+    assert idx.dtype == torch.int32 and strength.dtype == torch.float32 and idx.dim() == 2 and strength.shape == idx.shape
+    m = idx.shape[1]
+    assert 1 <= m <= 63, f"m={m} outside 1 .. 63"
+    R, ld_idx = _rows(idx, m, "idx")
+    _, ld_strength = _rows(strength, m, "strength")
+    nnz = col.shape[0]
+    _vec(rowptr, R + 1, torch.int64, "rowptr")
+    _vec(col, nnz, torch.int32, "col")
+    _vec(w, nnz, torch.float32, "w")
+
+    def launch():
+        if R == 0 or nnz == 0:
+            return
+        check(_lib.load().vf_umap_union(idx.data_ptr(), ld_idx, strength.data_ptr(), ld_strength, R, m, rowptr.data_ptr(),
+                                        col.data_ptr(), nnz, w.data_ptr(), _stream()), "vf_umap_union")
+    # bytes: per entry its column and weight, and two lists of m indices scanned (half of each on average)
+    _run(launch, lambda: ("umap_union", 3.0 * nnz, 4.0 * nnz * (2 + m) + 8.0 * R, f"R={R} m={m} nnz={nnz}", family or _SCOPE))
+    return w
+
+
+def umap_layout(rowptr: torch.Tensor, col: torch.Tensor, samples: torch.Tensor, y0: torch.Tensor, y1: torch.Tensor, *, epoch_begin: int,
+                epoch_end: int, n_epochs: int, a: float, b: float, gamma: float = 1.0, learning_rate: float = 1.0,
+                negative_sample_rate: int = 5, seed: int = 42, family: str = ""):
+    """The epochs [epoch_begin, epoch_end) of the UMAP layout (vf_umap_layout, include/vf_hip_umap.h), one kernel per epoch
+    launched from a loop inside the library: epoch epoch_begin reads y0 and writes y1, the next the other way round.  rowptr
+    int64 [R + 1], col int32 [nnz], samples int32 [nnz] contiguous, only read; y0, y1 fp32 [R, dim] row-strided with the same
+    stride, dim in 1 .. 8.  Every vertex reads the others where they stood when the epoch began and writes its own row alone:
+    no race, one result, and [0, 10) equals [0, 5) then [5, 10) bit for bit.  The caller owns every buffer and nothing is made
+    here.  Returns the buffer that holds the result: y0 if epoch_end - epoch_begin is even, y1 if it is odd."""
+    _dev(rowptr, col, samples, y0, y1)
+    assert y0.dtype == torch.float32 and y1.dtype == torch.float32 and y0.dim() == 2 and y0.shape == y1.shape
+    dim = y0.shape[1]
+    assert 1 <= dim <= 8, f"dim={dim} outside 1 .. 8"
+    R, ld = _rows(y0, dim, "y0")
+    _, ld1 = _rows(y1, dim, "y1")
+    assert ld == ld1, "y0 and y1 have one row stride"
+    nnz = col.shape[0]
+    _vec(rowptr, R + 1, torch.int64, "rowptr")
+    _vec(col, nnz, torch.int32, "col")
+    _vec(samples, nnz, torch.int32, "samples")
+    epochs = int(epoch_end) - int(epoch_begin)
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_umap_layout(rowptr.data_ptr(), col.data_ptr(), samples.data_ptr(), nnz, R, dim, y0.data_ptr(), y1.data_ptr(),
+                                         ld, int(epoch_begin), int(epoch_end), int(n_epochs), float(a), float(b), float(gamma),
+                                         float(learning_rate), int(negative_sample_rate), int(seed) & 0xFFFFFFFF, _stream()), "vf_umap_layout")
+    # per epoch: every entry's sample count and column walked, every row read and written; force evaluations are counted by the
+    # caller who knows the samples (scripts/umap_bench.py); here an upper figure of one per entry
+    _run(launch, lambda: ("umap_layout", 40.0 * max(epochs, 0) * nnz, 4.0 * max(epochs, 0) * (2 * nnz + 2 * R * dim) + 8.0 * R,
+                          f"R={R} dim={dim} nnz={nnz} epochs={epochs}", family or _SCOPE))
+    return y0 if epochs % 2 == 0 else y1
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

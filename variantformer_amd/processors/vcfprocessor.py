@@ -328,6 +328,27 @@ class VCFProcessor:
         leaves = linkage.leaves_list(Z)
         return {"Z": Z, "leaves": leaves, "labels": labels, "ordered_labels": [labels[i] for i in leaves]}
 
+    def expression_umap(self, df, on: str = "predicted_expression", axis: str = "genes", tissue=None, **umap_kwargs):
+        """The UMAP picture of a finished prediction, what the reference's vcf2embed notebook draws with
+        umap-learn: `df` is what format_output returned; the matrix is neighbors.from_predictions(df, on, axis, tissue) and the
+        k-NN graph, the fuzzy simplicial set and the layout run on the device (manifold.umap, which takes `umap_kwargs`:
+        n_neighbors=30, min_dist=0.1, metric="correlation", n_components=2, n_epochs, init="pca", seed=42, ...).  No model and
+        no checkpoint are involved.  Returns a dict:
+          coords   fp32 [rows, n_components], one row per row of the matrix;
+          labels   what names each row of the matrix.
+        Rows that are genes (axis="genes" with expression, or embeddings of one `tissue`) also get the columns umap_1 ..
+        umap_n of `df`, one number per gene.  Embeddings with tissue=None have (gene, tissue) rows: each gene's cell then holds
+        its tissues' coordinates, fp32 [tissues].  axis="tissues" has no gene rows and adds no column."""
+        from .. import manifold, neighbors
+        m, labels = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
+        coords = manifold.umap(m, **umap_kwargs)
+        if axis != "tissues":
+            per = len(labels) // len(df)                                 # 1, or the tissues of a (gene, tissue) row set
+            for c in range(coords.shape[1]):
+                column = coords[:, c] if per == 1 else list(coords[:, c].reshape(len(df), per))
+                df[f"umap_{c + 1}"] = pd.Series(column, index=df.index, dtype=np.float32 if per == 1 else object)
+        return {"coords": coords, "labels": labels}
+
     def predict_distributed(self, model, checkpoint_path, trainer, vcf_dataset, batch_size: int | None = None, costs=None,
                             **loader_kwargs):
         """Multi-GPU vcf2exp (the reference is single-device, vcfprocessor.py:252-258): call from every rank
