@@ -4,7 +4,11 @@
   find_ab(min_dist, spread)        the a, b of the curve 1 / (1 + a x^(2b)) that umap-learn fits with scipy, in plain numpy;
   fuzzy_graph(indices, distances)  the fuzzy simplicial set of a k-NN graph: (rowptr, col, w, rho, sigma);
   layout(graph, init, n_epochs, a, b, ...)   the SGD epochs over that graph from the positions `init`;
-  umap(x, ...)                     neighbors.knn, fuzzy_graph, an initialisation and layout, on the device throughout.
+  umap(x, ...)                     neighbors.knn, fuzzy_graph, an initialisation and layout, on the device throughout;
+  spectral_embedding(graph, n)     the eigenvectors of the graph's normalised Laplacian for its smallest non-trivial eigenvalues, by
+                                   Chebyshev-filtered subspace iteration on the device (include/vf_hip_spectral.h, DESIGN.md 5i);
+  spectral_init                    that embedding as a callable `init` of umap: umap-learn's default init="spectral";
+  graph_components(graph)          the graph's connected components (labels, count).
 
 Three entries of include/vf_hip_umap.h do the work: ops.umap_smooth_knn (rho, sigma, directed strengths),
 ops.umap_union (the fuzzy union over the symmetric graph, whose CSR arrays are built here with torch: index plumbing) and
@@ -12,11 +16,15 @@ ops.umap_layout (all epochs of a call from one loop inside the library).  The la
 they stood when the epoch began and writes only its own row, so a run has one result, bit for bit, whatever the hardware does,
 and can be split at any epoch.  Two deliberate differences from umap-learn follow from that and are stated in DESIGN.md 5h: others
 are read at epoch-start positions (umap-learn reads and writes them concurrently), and every drawn edge gets exactly
-negative_sample_rate repulsions (umap-learn keeps a float schedule).  Spectral initialisation is out of scope (it needs a sparse
-eigensolver): init is "pca", "random" or an array.  transform() of new points is out of scope too.  There is no CPU path: without
+negative_sample_rate repulsions (umap-learn keeps a float schedule).  init is "pca", "random", an array or a callable
+f(graph, n_components, seed) -> positions; umap-learn's default start is init=spectral_init (the string "spectral" stays refused
+and names it).  On a disconnected graph spectral_init falls back to the random initialisation with a warning: umap-learn's
+per-component layout is out of scope.  transform() of new points is out of scope too.  There is no CPU path: without
 a GPU the calls raise, after their arguments have been checked.  scipy, umap-learn, numba and pynndescent are not imported.
 """
 from __future__ import annotations
+
+import warnings
 
 import numpy as np
 import torch
@@ -246,16 +254,271 @@ def rescale(y: torch.Tensor) -> torch.Tensor:
     return torch.where(span > 0, 10.0 * (y - lo) / torch.where(span > 0, span, torch.ones_like(span)), torch.zeros_like(y))
 
 
+# ---- the spectral embedding ----------------------------------------------------------------------------------------------------------
+SPECTRAL_BLOCK_MAX = 32                    # VF_SPECTRAL_MAX_P
+FILTER_LOW, FILTER_HIGH = -0.99, 1.0 - 1e-7   # where the upper end of the damped interval is held
+ORTH_FLOOR = 1e-14                         # eigenvalues of the scaled Gram matrix below this share of the largest are raised to it
+_ONE_STEP = np.array([[1.0, 0.0, 0.0]], dtype=np.float32)
+
+
+def _graph_members(graph):
+    if not isinstance(graph, (tuple, list)) or len(graph) < 3:
+        raise ValueError("graph must be what fuzzy_graph returned: (rowptr, col, w, ...)")
+    for v, name in zip(graph[:3], ("rowptr", "col", "w")):
+        if not isinstance(v, (np.ndarray, torch.Tensor)) or v.ndim != 1:
+            raise ValueError(f"graph: {name} must be a vector (numpy or torch)")
+    R = graph[0].shape[0] - 1
+    if R < 0 or R > 1 << 24 or graph[1].shape[0] != graph[2].shape[0]:
+        raise ValueError("graph: rowptr must hold 1 .. 2^24 + 1 offsets, and col and w one entry each per edge")
+    return R
+
+
+def _graph_tensors(graph):
+    return (_tensor(graph[0], torch.int64).contiguous(), _tensor(graph[1], torch.int32).contiguous(), _tensor(graph[2], torch.float32).contiguous())
+
+
+def _components(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor):
+    R = rowptr.shape[0] - 1
+    dev = rowptr.device
+    labels = torch.arange(R, dtype=torch.int64, device=dev)
+    if R == 0:
+        return labels.to(torch.int32), 0
+    rows = torch.repeat_interleave(torch.arange(R, dtype=torch.int64, device=dev), rowptr[1:] - rowptr[:-1])
+    cols = col.to(torch.int64)
+    edge = (w > 0) & (cols >= 0) & (cols < R)                             # an entry without a positive weight is no edge
+    rows, cols = rows[edge], cols[edge]
+    jumps = max(int(R - 1).bit_length(), 1)
+    for _ in range(R + 1):
+        new = labels.scatter_reduce(0, rows, labels[cols], "amin", include_self=True)       # an integer minimum: one result
+        for _ in range(jumps):                                            # pointer jumping: a label is a vertex of the component
+            new = new[new]
+        if not bool((new != labels).any()):                               # the round's one scalar
+            return labels.to(torch.int32), int((labels == torch.arange(R, dtype=torch.int64, device=dev)).sum())
+        labels = new
+    raise RuntimeError(f"graph_components did not settle in {R + 1} rounds")
+
+
+def graph_components(graph):
+    """(labels int32 [R], count): the connected components of `graph` -- what fuzzy_graph returned, or (rowptr, col, w) -- by
+    min-label propagation over the edges with pointer jumping, on the device in torch (index plumbing, as the CSR construction
+    is); a round reads one scalar back, rounds are bounded by R.  A label is the smallest vertex of its component; a vertex
+    without an edge is a component of its own; an entry whose weight is not positive is no edge.  labels has the type of the
+    graph's members."""
+    _graph_members(graph)
+    _need_gpu()
+    labels, count = _components(*_graph_tensors(graph))
+    return neighbors._back(graph[0], labels)[0], count
+
+
+def chebyshev_coefficients(bound: float, degree: int) -> np.ndarray:
+    """fp32 [degree, 3]: the coefficients ops.spmm_recur takes for the degree-`degree` Chebyshev filter p(S) that damps the
+    eigenvalues in [-1, bound] (|p| <= p(bound)) and has p(1) = 1.  In fp64, rounded once: with c = (bound - 1) / 2,
+    e = (bound + 1) / 2, sigma_1 = e / (1 - c): step 0 is (sigma_1 / e, -c sigma_1 / e, 0); step t >= 1 has
+    sigma' = 1 / (2 / sigma_1 - sigma) and is (2 sigma' / e, -2 sigma' c / e, -sigma sigma'), then sigma = sigma'."""
+    c, e = (bound - 1.0) / 2.0, (bound + 1.0) / 2.0
+    sigma1 = e / (1.0 - c)
+    sigma = sigma1
+    coef = np.zeros((degree, 3), dtype=np.float64)
+    coef[0] = (sigma1 / e, -c * sigma1 / e, 0.0)
+    for t in range(1, degree):
+        nxt = 1.0 / (2.0 / sigma1 - sigma)
+        coef[t] = (2.0 * nxt / e, -2.0 * nxt * c / e, -sigma * nxt)
+        sigma = nxt
+    return coef.astype(np.float32)
+
+
+def orthonormalising_matrix(G: np.ndarray) -> np.ndarray:
+    """fp64 [p, p] T with X T orthonormal, from G = X^T X, for a block whose column 0 is the locked trivial eigenvector: column 0
+    of T is the unit vector (X T keeps it bit for bit); the other columns are first made orthogonal to it (c = G[0, 1:] / G[0, 0],
+    G' = G[1:, 1:] - G[0, 0] c c^T), then G' is scaled to a unit diagonal by d = sqrt(diag G'), decomposed as V diag(lam) V^T
+    (lam raised to ORTH_FLOOR max(lam) at least), and M = diag(1 / d) V diag(lam^-1/2); T[0, 1:] = -c M, T[1:, 1:] = M.  No
+    Cholesky factor: a filtered block is too ill-conditioned for one.  Applied twice."""
+    p = G.shape[0]
+    T = np.zeros((p, p), dtype=np.float64)
+    T[0, 0] = 1.0
+    if p == 1:
+        return T
+    c = G[0, 1:] / G[0, 0]
+    Gp = G[1:, 1:] - G[0, 0] * np.outer(c, c)
+    Gp = (Gp + Gp.T) / 2.0
+    d = np.sqrt(np.where(np.diag(Gp) > 0, np.diag(Gp), 1.0))
+    lam, V = np.linalg.eigh(Gp / np.outer(d, d))
+    lam = np.maximum(lam, ORTH_FLOOR * max(lam.max(), np.finfo(np.float64).tiny))
+    M = (V / np.sqrt(lam)[None, :]) / d[:, None]
+    T[0, 1:] = -c @ M
+    T[1:, 1:] = M
+    return T
+
+
+def _spectral(rowptr, col, w, deg, dinv, k: int, block: int, degree: int, tol: float, max_iter: int, seed: int):
+    """The eigensolver on a connected graph with positive degrees: (vectors fp32 [R, k] on the device, info)."""
+    R = rowptr.shape[0] - 1
+    dev = rowptr.device
+    p = min(block, R)
+    bufs = [torch.empty((R, p), dtype=torch.float32, device=dev) for _ in range(3)]
+    work = torch.empty(ops.TALL_GRAM_MAX_BLOCKS * p * p, dtype=torch.float64, device=dev)
+    products = 0
+
+    def gram(a, b):
+        out = torch.empty((a.shape[1], b.shape[1]), dtype=torch.float64, device=dev)
+        return ops.tall_gram(a, b, out=out, work=work, family="spectral").cpu().numpy()
+
+    def others(x):
+        return [b for b in bufs if b is not x]
+
+    def recur(x, coef):
+        nonlocal products
+        o = others(x)
+        products += coef.shape[0]
+        return ops.spmm_recur(rowptr, col, w, dinv, x, o[0], o[1], coef, family="spectral")
+
+    def times(x, T):
+        return ops.tall_mul(x, torch.from_numpy(np.ascontiguousarray(T)).to(dev), out=others(x)[0], family="spectral")
+
+    def orthonormalise(x):
+        for _ in range(2):
+            x = times(x, orthonormalising_matrix(gram(x, x)))
+        return x
+
+    def rayleigh_ritz(x):
+        H = gram(x, recur(x, _ONE_STEP))
+        H = (H + H.T) / 2.0
+        lam, Q = np.linalg.eigh(H[1:, 1:]) if p > 1 else (np.zeros(0), np.zeros((0, 0)))
+        lam, Q = lam[::-1], Q[:, ::-1]                                  # descending in S: ascending in L = I - S
+        T = np.zeros((p, p), dtype=np.float64)
+        T[0, 0] = 1.0
+        T[1:, 1:] = Q
+        theta = np.concatenate(([H[0, 0]], lam))
+        x = times(x, T)
+        sx = recur(x, _ONE_STEP)
+        th = torch.from_numpy(theta[:k + 1].astype(np.float32)).to(dev)
+        r = sx[:, :k + 1] - x[:, :k + 1] * th[None, :]
+        return x, theta, np.sqrt(np.diag(gram(r, r)))
+
+    # the trivial eigenvector sqrt(deg) / ||sqrt(deg)|| is locked as column 0; the other columns start from the hash
+    x = bufs[0]
+    x.copy_(random_init(R, p, seed, dev) - 0.5)
+    v0 = torch.sqrt(deg)
+    v0 = v0 * float(1.0 / np.sqrt(gram(v0[:, None], v0[:, None])[0, 0]))
+    x[:, 0] = v0
+    x, theta, res = rayleigh_ritz(orthonormalise(x))
+    iterations = 0
+    while res[1:k + 1].max() >= tol and iterations < max_iter:
+        iterations += 1
+        bound = min(max(float(theta[-1]), FILTER_LOW), FILTER_HIGH)      # the block's smallest Ritz value
+        x = recur(x, chebyshev_coefficients(bound, degree))
+        x[:, 0] = v0
+        x, theta, res = rayleigh_ritz(orthonormalise(x))
+    converged = bool(res[1:k + 1].max() < tol)
+    if not converged:
+        warnings.warn(f"spectral_embedding stopped at max_iter={max_iter} with a residual of {res[1:k + 1].max():.3e} (tol={tol:g})",
+                      RuntimeWarning, stacklevel=3)
+    y = x[:, 1:k + 1]
+    y = y * torch.from_numpy((1.0 / np.sqrt(np.diag(gram(y, y)))).astype(np.float32)).to(dev)[None, :]
+    big = y.abs().argmax(0)                                               # the first of equal magnitudes
+    y = y * torch.where(y[big, torch.arange(k, device=dev)] < 0, -1.0, 1.0)[None, :]
+    info = dict(eigenvalues=1.0 - theta[:k + 1], residuals=res[:k + 1].copy(), iterations=iterations, products=products, converged=converged)
+    return y.contiguous(), info
+
+
+def _check_spectral_args(n_components, block, degree, tol, max_iter, seed):
+    n_components = _int_in(n_components, "n_components", 1, DIM_MAX)
+    block = _int_in(block, "block", n_components + 1, SPECTRAL_BLOCK_MAX)
+    return (n_components, block, _int_in(degree, "degree", 2, 1 << 16), _number(tol, "tol", 0.0, True),
+            _int_in(max_iter, "max_iter", 0, 1 << 20), _int_in(seed, "seed", 0, 2 ** 32 - 1))
+
+
+def _degrees(rowptr, col, w):
+    R = rowptr.shape[0] - 1
+    deg = torch.empty(R, dtype=torch.float32, device=rowptr.device)
+    dinv = torch.empty(R, dtype=torch.float32, device=rowptr.device)
+    return ops.graph_degree(rowptr, col, w, deg=deg, dinv_sqrt=dinv, family="spectral")
+
+
+def spectral_embedding(graph, n_components: int = 2, *, block: int = 16, degree: int = 40, tol: float = 1e-4, max_iter: int = 50,
+                       seed: int = 42, return_info: bool = False):
+    """fp32 [R, n_components], of the type of the graph's members: the eigenvectors of the normalised Laplacian
+    L = I - D^-1/2 W D^-1/2 of `graph` -- what fuzzy_graph returned, or (rowptr, col, w) -- for its 2nd .. (n_components + 1)-th
+    smallest eigenvalues, ascending: what umap-learn's spectral_layout takes.  Each has unit norm and is signed so that its
+    largest-magnitude component is positive (the first of equal ones), pca_init's rule.
+
+    Chebyshev-filtered subspace iteration on the device (include/vf_hip_spectral.h) in S = D^-1/2 W D^-1/2, whose
+    largest eigenvalues are L's smallest.  The block has p = min(block, R) columns.  Column 0 is LOCKED to the known trivial
+    eigenvector sqrt(deg) / ||sqrt(deg)||: it is set, never iterated, and every orthonormalisation projects the others against
+    it.  The others start from random_init(R, p, seed) - 0.5.  Orthonormalisation is X <- X T with T from the eigen-decomposition
+    of the column-scaled fp64 Gram matrix (orthonormalising_matrix), applied twice; Rayleigh-Ritz takes H = X^T (S X) through
+    ops.tall_gram, numpy's eigh of the symmetrised matrix in fp64 on the host, X <- X Q, and the residuals ||S x - theta x||_2 of
+    the rotated columns from a fresh product.  Every outer iteration applies chebyshev_coefficients(bound, degree) through one
+    ops.spmm_recur call, bound the block's smallest Ritz value held in [-0.99, 1 - 1e-7], then orthonormalises and rotates again;
+    it stops when the wanted residuals are below tol, or at max_iter with a RuntimeWarning that states the worst residual (the
+    current vectors are returned).  X Q and X T are ops.tall_mul, the library's own kernel: nothing of the solver's arithmetic
+    is torch's but elementwise operations, so two runs are equal bit for bit.
+
+    return_info=True: (vectors, dict) with `eigenvalues` (of L, fp64, n_components + 1 of them: the trivial one first),
+    `residuals` (likewise), `iterations` (outer), `products` (sparse block products S Y) and `converged`.
+    ValueError before the device is touched: n_components outside 1 .. 8, block outside n_components + 1 .. 32, degree < 2,
+    tol <= 0.  ValueError after the degrees and components have been computed on the device: R < n_components + 2; a graph of
+    more than one component (isolated vertices count; the message states how many)."""
+    R = _graph_members(graph)
+    k, block, degree, tol, max_iter, seed = _check_spectral_args(n_components, block, degree, tol, max_iter, seed)
+    _need_gpu()
+    rowptr, col, w = _graph_tensors(graph)
+    deg, dinv = _degrees(rowptr, col, w)
+    _, count = _components(rowptr, col, w)
+    if R < k + 2:
+        raise ValueError(f"spectral_embedding needs at least n_components + 2 = {k + 2} vertices, the graph has {R}")
+    if count != 1:
+        raise ValueError(f"spectral_embedding needs a connected graph, this one has {count} components (isolated vertices count)")
+    if not bool((deg > 0).all()):
+        raise ValueError("spectral_embedding needs positive degrees: the weights of some vertex do not sum to a positive number")
+    y, info = _spectral(rowptr, col, w, deg, dinv, k, block, degree, tol, max_iter, seed)
+    y = neighbors._back(graph[0], y)[0]
+    return (y, info) if return_info else y
+
+
+def spectral_init(graph, n_components: int, seed: int):
+    """An `init` for umap: spectral_embedding(graph, n_components, seed=seed) on a connected graph of at least n_components + 2
+    vertices.  Otherwise a RuntimeWarning that names the number of components or the size, and random_init(R, n_components,
+    seed): umap-learn's own fallback when its eigensolver fails (its per-component layout of a disconnected graph is not
+    done here).  Well-separated clusters do disconnect a k-NN graph, so the fallback is no rarity.  Returns a tensor on the
+    device."""
+    R = _graph_members(graph)
+    k, _, _, _, _, seed = _check_spectral_args(n_components, SPECTRAL_BLOCK_MAX, 40, 1e-4, 50, seed)
+    _need_gpu()
+    rowptr, col, w = _graph_tensors(graph)
+    if R < k + 2:
+        warnings.warn(f"spectral_init: {R} vertices are fewer than n_components + 2 = {k + 2}; the random initialisation is used", RuntimeWarning, stacklevel=2)
+        return random_init(R, k, seed, rowptr.device)
+    deg, dinv = _degrees(rowptr, col, w)
+    _, count = _components(rowptr, col, w)
+    if count != 1 or not bool((deg > 0).all()):
+        warnings.warn(f"spectral_init: the graph has {count} components (isolated vertices count); the random initialisation is used",
+                      RuntimeWarning, stacklevel=2)
+        return random_init(R, k, seed, rowptr.device)
+    return _spectral(rowptr, col, w, deg, dinv, k, 16, 40, 1e-4, 50, seed)[0]
+
+
 # ---- the whole ---------------------------------------------------------------------------------------------------------------------
+def _called_init(init, graph, R: int, n_components: int, seed: int):
+    """What the callable `init` returns for (graph, n_components, seed), refused unless it is positions [R, n_components]."""
+    y = init(graph, n_components, seed)
+    if not isinstance(y, (np.ndarray, torch.Tensor)) or tuple(y.shape) != (R, n_components):
+        raise ValueError(f"init: the callable must return positions [{R}, {n_components}] (numpy or torch), not "
+                         f"{tuple(y.shape) if hasattr(y, 'shape') else type(y).__name__}")
+    return y
+
+
 def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correlation", n_components: int = 2, n_epochs=None,
          init="pca", seed: int = 42, negative_sample_rate: int = 5, repulsion_strength: float = 1.0, learning_rate: float = 1.0):
     """The UMAP embedding of the rows of x [R, d] (numpy or torch): fp32 [R, n_components] of the type of x.
 
     n_neighbors 2 .. 64 counts the row itself as umap-learn does: the graph is neighbors.knn(x, n_neighbors - 1, metric).
     min_dist 0 .. 1 gives the curve through find_ab (spread 1).  n_epochs None: 500 for R <= 10000, else 200.  init: "pca"
-    (d >= n_components), "random" (counter-based from `seed`) or an array [R, n_components]; every init is rescaled per coordinate
-    to [0, 10] and no noise is added.  Spectral initialisation is out of scope (it needs a sparse eigensolver), and so is
-    transform() of new points.  seed also fixes the negative samples: the result is a function of the arguments, bit for bit.
+    (d >= n_components), "random" (counter-based from `seed`), an array [R, n_components] or a callable
+    f(graph, n_components, seed) -> positions [R, n_components] (numpy or torch; graph = (rowptr, col, w), the device tensors of
+    the fuzzy graph; a result of another shape is refused); every init is rescaled per coordinate to [0, 10] and no noise is
+    added.  init=manifold.spectral_init is umap-learn's default spectral start (the string "spectral" is refused and names it).
+    transform() of new points is out of scope.  seed also fixes the negative samples: the result is a function of the arguments, bit for bit.
     Differences from umap-learn, deliberate: other vertices are read where they stood when the epoch began, and
     every drawn edge gets exactly negative_sample_rate repulsions."""
     neighbors._check_matrix(x, "x")
@@ -272,12 +535,16 @@ def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correla
     if n_epochs is None:
         n_epochs = 500 if R <= 10000 else 200
     if isinstance(init, str):
+        if init == "spectral":
+            raise ValueError("init='spectral' is not a name here: pass init=manifold.spectral_init, the callable")
         if init not in INITS:
-            raise ValueError(f"init must be one of {INITS} or an array [rows, n_components], not {init!r}")
+            raise ValueError(f"init must be one of {INITS}, an array [rows, n_components] or a callable such as manifold.spectral_init, not {init!r}")
         if init == "pca" and x.shape[1] < n_components:
             raise ValueError(f"init='pca' needs at least n_components={n_components} columns, x has {x.shape[1]}")
+    elif callable(init):
+        pass                                                              # its result is checked when it has been called
     elif not isinstance(init, (np.ndarray, torch.Tensor)) or tuple(init.shape) != (R, n_components):
-        raise ValueError(f"init must be one of {INITS} or an array [{R}, {n_components}]")
+        raise ValueError(f"init must be one of {INITS}, a callable or an array [{R}, {n_components}]")
     a, b = find_ab(min_dist)
     n_epochs, a, b, gamma, learning_rate, negative_sample_rate, seed = _check_layout_args(
         n_epochs, a, b, repulsion_strength, learning_rate, negative_sample_rate, seed)
@@ -286,6 +553,8 @@ def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correla
     rowptr, col, w, _, _ = _fuzzy_graph(idx, dist)
     if isinstance(init, str):
         y = pca_init(t, n_components) if init == "pca" else random_init(R, n_components, seed, t.device)
+    elif callable(init):
+        y = _tensor(_called_init(init, (rowptr, col, w), R, n_components, seed), torch.float32)
     else:
         y = _tensor(init, torch.float32)
     y = _layout(rowptr, col, w, rescale(y).contiguous(), n_epochs, a, b, gamma, learning_rate, negative_sample_rate, seed)

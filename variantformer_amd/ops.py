@@ -9,6 +9,7 @@ import contextlib
 import contextvars
 import math
 
+import numpy as np
 import torch
 
 from . import _lib, runtime
@@ -1038,6 +1039,111 @@ def umap_layout(rowptr: torch.Tensor, col: torch.Tensor, samples: torch.Tensor, 
     _run(launch, lambda: ("umap_layout", 40.0 * max(epochs, 0) * nnz, 4.0 * max(epochs, 0) * (2 * nnz + 2 * R * dim) + 8.0 * R,
                           f"R={R} dim={dim} nnz={nnz} epochs={epochs}", family or _SCOPE))
     return y0 if epochs % 2 == 0 else y1
+
+
+def _csr(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor):
+    """(vertices, entries) of a CSR graph: rowptr int64 [R + 1], col int32 [nnz], w fp32 [nnz], contiguous."""
+    assert rowptr.dim() == 1 and rowptr.shape[0] >= 1, "rowptr: int64 [R + 1]"
+    R, nnz = rowptr.shape[0] - 1, col.shape[0]
+    _vec(rowptr, R + 1, torch.int64, "rowptr")
+    _vec(col, nnz, torch.int32, "col")
+    _vec(w, nnz, torch.float32, "w")
+    return R, nnz
+
+
+def graph_degree(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, *, deg: torch.Tensor, dinv_sqrt: torch.Tensor, family: str = ""):
+    """The weighted degree of every vertex of a CSR graph and its inverse square root (vf_graph_degree,
+    include/vf_hip_spectral.h): deg[i] the sum of row i's w in the header's fixed order, dinv_sqrt[i] = 1 / sqrt(deg[i]) where
+    deg[i] > 0 and +0 elsewhere.  rowptr int64 [R + 1], col int32 [nnz], w fp32 [nnz], deg and dinv_sqrt fp32 [R], contiguous.
+    The caller owns every buffer and nothing is made here.  Returns (deg, dinv_sqrt)."""
+    _dev(rowptr, col, w, deg, dinv_sqrt)
+    R, nnz = _csr(rowptr, col, w)
+    _vec(deg, R, torch.float32, "deg")
+    _vec(dinv_sqrt, R, torch.float32, "dinv_sqrt")
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_graph_degree(rowptr.data_ptr(), col.data_ptr(), w.data_ptr(), nnz, R, deg.data_ptr(), dinv_sqrt.data_ptr(),
+                                          _stream()), "vf_graph_degree")
+    _run(launch, lambda: ("graph_degree", 1.0 * nnz, 4.0 * nnz + 16.0 * R, f"R={R} nnz={nnz}", family or _SCOPE))
+    return deg, dinv_sqrt
+
+
+def spmm_recur(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, dinv_sqrt: torch.Tensor, x0: torch.Tensor, x1: torch.Tensor,
+               x2: torch.Tensor, coef, *, family: str = ""):
+    """coef.shape[0] steps of Z = coef[t][0] * (S Y) + coef[t][1] * Y + coef[t][2] * W with S = D^-1/2 W D^-1/2 (vf_spmm_recur,
+    include/vf_hip_spectral.h), one kernel per step launched from a loop inside the library.  x0 holds the newest block, x2 the
+    one before it, x1 is overwritten first; step t reads x[t mod 3] and x[(t + 2) mod 3] and writes x[(t + 1) mod 3].  x0, x1, x2
+    fp32 [R, p] row-strided with one stride, p in 1 .. 32, three distinct buffers.  coef: a HOST numpy array fp32 [steps, 3],
+    read before the call returns; a coefficient of exactly 0 skips its term, whose operand is then not read.  The caller owns
+    every buffer and nothing is made here.  Returns the buffer that holds the result: x[steps mod 3]."""
+    _dev(rowptr, col, w, dinv_sqrt, x0, x1, x2)
+    R, nnz = _csr(rowptr, col, w)
+    _vec(dinv_sqrt, R, torch.float32, "dinv_sqrt")
+    assert x0.dtype == x1.dtype == x2.dtype == torch.float32 and x0.dim() == 2 and x0.shape == x1.shape == x2.shape and x0.shape[0] == R
+    p = x0.shape[1]
+    assert 1 <= p <= 32, f"p={p} outside 1 .. 32"
+    ld = _rows(x0, p, "x0")[1]
+    assert ld == _rows(x1, p, "x1")[1] == _rows(x2, p, "x2")[1], "x0, x1 and x2 have one row stride"
+    assert isinstance(coef, np.ndarray) and coef.dtype == np.float32 and coef.ndim == 2 and coef.shape[1] == 3 and coef.flags.c_contiguous, \
+        "coef: a host numpy array fp32 [steps, 3]"
+    steps = coef.shape[0]
+
+    def launch():
+        if R == 0 or steps == 0:
+            return
+        check(_lib.load().vf_spmm_recur(rowptr.data_ptr(), col.data_ptr(), w.data_ptr(), nnz, R, dinv_sqrt.data_ptr(), p, x0.data_ptr(),
+                                        x1.data_ptr(), x2.data_ptr(), ld, steps, coef.ctypes.data, _stream()), "vf_spmm_recur")
+    # per step: every entry's column, weight and the neighbour's scale, a row of p values gathered per entry, the block read
+    # twice and written once
+    _run(launch, lambda: ("spmm_recur", steps * (2.0 * nnz * p + nnz + 6.0 * R * p), steps * (4.0 * nnz * (3 + p) + 12.0 * R * p + 12.0 * R),
+                          f"R={R} p={p} nnz={nnz} steps={steps}", family or _SCOPE))
+    return (x0, x1, x2)[steps % 3]
+
+
+TALL_GRAM_MAX_BLOCKS = 1024                # VF_TALL_GRAM_MAX_BLOCKS: the workspace of tall_gram holds at most this many p x q partials
+
+
+def tall_gram(a: torch.Tensor, b: torch.Tensor, *, out: torch.Tensor, work: torch.Tensor, family: str = ""):
+    """out = a^T b in fp64 (vf_tall_gram, include/vf_hip_spectral.h): a fp32 [R, p] and b fp32 [R, q] row-strided (they may be
+    one tensor), p and q in 1 .. 32; out fp64 [p, q] contiguous; work a contiguous fp64 workspace of at least
+    ceil(R / chunk) * p * q elements, chunk as the header states it (1024 * p * q always suffice).  Products and sums in fp64 in two stages of fixed
+    order, no atomics: two runs are equal bit for bit.  The caller owns every buffer and nothing is made here.  Returns out."""
+    _dev(a, b, out, work)
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0]
+    p, q = a.shape[1], b.shape[1]
+    assert 1 <= p <= 32 and 1 <= q <= 32, f"p={p}, q={q} outside 1 .. 32"
+    R, lda = _rows(a, p, "a")
+    ldb = _rows(b, q, "b")[1]
+    assert out.dtype == torch.float64 and tuple(out.shape) == (p, q) and out.is_contiguous(), "out: a contiguous fp64 [p, q]"
+    chunk = 64 * max(-(-R // (64 * TALL_GRAM_MAX_BLOCKS)), 1)          # the header's partition: nb = ceil(R / chunk) <= 1024 partials
+    assert work.dtype == torch.float64 and work.dim() == 1 and work.is_contiguous() and work.shape[0] >= -(-R // chunk) * p * q, \
+        "work: fp64, at least ceil(R / chunk) * p * q elements (1024 * p * q always suffice)"
+
+    def launch():
+        check(_lib.load().vf_tall_gram(a.data_ptr(), lda, b.data_ptr(), ldb, R, p, q, out.data_ptr(), work.data_ptr(), _stream()), "vf_tall_gram")
+    _run(launch, lambda: ("tall_gram", 2.0 * R * p * q, 4.0 * R * (p + q) + 8.0 * p * q, f"R={R} p={p} q={q}", family or _SCOPE))
+    return out
+
+
+def tall_mul(x: torch.Tensor, t: torch.Tensor, *, out: torch.Tensor, family: str = ""):
+    """out = x t with the sum in fp64, rounded once to fp32 (vf_tall_mul, include/vf_hip_spectral.h): x fp32 [R, p] row-strided,
+    t fp64 [p, q] contiguous on the device, out fp32 [R, q] row-strided, not overlapping x; p and q in 1 .. 32.  One thread per
+    output element, k ascending.  The caller owns every buffer and nothing is made here.  Returns out."""
+    _dev(x, t, out)
+    assert x.dtype == torch.float32 and out.dtype == torch.float32 and t.dtype == torch.float64 and x.dim() == 2 and t.dim() == 2 and out.dim() == 2
+    p, q = t.shape
+    assert 1 <= p <= 32 and 1 <= q <= 32 and t.is_contiguous() and x.shape[1] == p and out.shape[1] == q and x.shape[0] == out.shape[0]
+    R, ldx = _rows(x, p, "x")
+    ldo = _rows(out, q, "out")[1]
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_tall_mul(x.data_ptr(), ldx, R, p, t.data_ptr(), q, out.data_ptr(), ldo, _stream()), "vf_tall_mul")
+    _run(launch, lambda: ("tall_mul", 2.0 * R * p * q, 4.0 * R * (p + q) + 8.0 * p * q, f"R={R} p={p} q={q}", family or _SCOPE))
+    return out
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,

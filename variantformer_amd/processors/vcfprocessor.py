@@ -332,8 +332,9 @@ class VCFProcessor:
         """The UMAP picture of a finished prediction, what the reference's vcf2embed notebook draws with
         umap-learn: `df` is what format_output returned; the matrix is neighbors.from_predictions(df, on, axis, tissue) and the
         k-NN graph, the fuzzy simplicial set and the layout run on the device (manifold.umap, which takes `umap_kwargs`:
-        n_neighbors=30, min_dist=0.1, metric="correlation", n_components=2, n_epochs, init="pca", seed=42, ...).  No model and
-        no checkpoint are involved.  Returns a dict:
+        n_neighbors=30, min_dist=0.1, metric="correlation", n_components=2, n_epochs, init="pca", seed=42, ...; init=manifold.spectral_init
+        starts from the eigenvectors of the fuzzy graph's normalised Laplacian, umap-learn's default).  No
+        model and no checkpoint are involved.  Returns a dict:
           coords   fp32 [rows, n_components], one row per row of the matrix;
           labels   what names each row of the matrix.
         Rows that are genes (axis="genes" with expression, or embeddings of one `tissue`) also get the columns umap_1 ..
