@@ -1,0 +1,149 @@
+/* vf_hip_umap_transform.h -- the entries of libvf_hip.so that place NEW rows in a fitted UMAP embedding (umap-learn's transform):
+ * the directed membership strengths of every query's list of training neighbours, the start of every query as the strength-
+ * weighted mean of its neighbours' positions, and the epochs of the SGD layout in which the training points stand still.  A
+ * query vertex then depends on nothing that moves except itself: all of its epochs run in one kernel, its neighbours' positions
+ * are loaded once and held in registers, and only the negative samples are gathered, at addresses that do not depend on the
+ * positions.  The stages are driven by variantformer_amd/manifold.py (fit, UMAPModel.transform), which finds the neighbours with
+ * vf_knn_dot and forms the draw counts with torch.
+ *
+ * The eleventh header of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h, vf_hip_linkage.h, vf_hip_umap.h and vf_hip_spectral.h.  Its entries are
+ * bound through _lib.UMAP_TRANSFORM_SIGNATURES, which _lib.load() applies like the other ten tables, and
+ * tests/umap_transform_cases.py holds their references and case table.  Everything the main header says holds here: the
+ * conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok / VF_ERR_*,
+ * vf_last_error()), the comment contract of every entry, and VF_ABI_VERSION: a new symbol changes no existing one, so the
+ * version stays 13.  The due rule, the hash, clip and the curve are those of vf_hip_umap.h and are restated here in full.
+ *
+ * Nothing in this header's code is contracted into a fused multiply-add; exp and pow are the compiler's fp32 library functions,
+ * so sigma, the strengths below 1 and the positions are held to fp64 restatements within measured bounds
+ * (tests/umap_transform_cases.py), and every selection, every integer (the due rule, the hash, the negative vertex) and the
+ * start (vf_umap_init_transform, which calls neither) exactly.
+ */
+#ifndef VF_HIP_UMAP_TRANSFORM_H
+#define VF_HIP_UMAP_TRANSFORM_H
+
+#include "vf_hip.h"
+#include "vf_hip_umap.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* the longest list of training neighbours: m = n_neighbors <= 64 (a query is no training row, nothing is excluded), one lane
+ * of a wavefront per neighbour */
+#define VF_UMAP_TRANSFORM_MAX_M 64
+/* the most epochs one kernel launch of vf_umap_layout_transform runs: the library loops over launches, so that no single
+ * kernel's run time grows with N */
+#define VF_UMAP_TRANSFORM_EPOCHS_PER_LAUNCH 8
+
+/* sigma and the directed membership strengths of every query's list of training neighbours (added under ABI 13): umap-learn's
+ * smooth_knn_dist with local_connectivity - 1 = 0, hence rho = +0 for every row, followed by its bipartite
+ * compute_membership_strengths.  vf_umap_smooth_knn with three differences: there is no rho, the target counts m entries and
+ * no row itself, and an index equal to the row's own number is a training row like any other.
+ * Arguments:
+ *   idx        int32 [Rq, >= m], rows ld_idx apart, and  dist  fp32 [Rq, >= m], rows ld_dist apart (64-bit offsets): the m
+ *              training rows nearest to each query and their distances, as neighbors.knn(x, m, queries=q) returns them;
+ *              Rq  query rows;  m  entries per row, 1 .. VF_UMAP_TRANSFORM_MAX_M;
+ *   mean_dist  fp32: the mean of the present distances OF THE FIT (the model's, not this batch's: a query's result then
+ *              depends on that query alone);
+ *   sigma      fp32 [Rq];  strength  fp32 [Rq, >= m], rows ld_strength apart.
+ * An entry is ABSENT if its index is negative or its distance is NaN, +Inf or -Inf; every other entry is present.  An absent
+ * entry contributes to nothing below.
+ * Write set, exactly: sigma[i] and strength[i * ld_strength + t] for 0 <= i < Rq, 0 <= t < m.  idx and dist are only read, at
+ * [i, t] with t < m.
+ * Arithmetic, per row, in fp32:
+ *   sigma  by bisection with lo = 0, hi = Inf, mid = 1 and target = log2(m) (the fp32 nearest to the fp64 value), for at most
+ *          VF_UMAP_SMOOTH_ITERS iterations: sum = over the present entries, in the butterfly over the lanes that
+ *          vf_umap_smooth_knn uses, of (d > 0 ? exp(-(d / mid)) : 1); stop if |sum - target| < VF_UMAP_SMOOTH_TOL; if
+ *          sum > target then hi = mid, mid = (lo + hi) / 2; else lo = mid and mid = (hi == Inf ? mid * 2 : (lo + hi) / 2).
+ *          sigma = mid, then the floor: sigma = max(sigma, VF_UMAP_MIN_SCALE * mean_dist);
+ *   a row with no present entry: sigma = +0, every strength +0;
+ *   strength[i, t] = +0 if the entry is absent; 1 if d <= 0 or sigma == 0; exp(-(d / sigma)) otherwise.  idx[i, t] == i is NOT
+ *   zeroed: it names a training row.
+ * One wavefront per row, one lane per entry.
+ * Non-finite operands: a NaN or infinite distance makes its entry absent, and the row is computed from the rest.  A NaN
+ * mean_dist never raises the floor; an infinite one makes sigma of every row with a present entry +Inf and its strengths 1.
+ * Refused before anything is launched (VF_ERR_INVALID_ARG, the argument named in vf_last_error()): a null idx, dist, sigma or
+ * strength; any of the four not 4-byte aligned; m outside 1 .. VF_UMAP_TRANSFORM_MAX_M; Rq < 0; Rq > VF_UMAP_MAX_R (2^24);
+ * ld_idx, ld_dist or ld_strength < m.  Rq == 0 is VF_OK with nothing launched.
+ * Not checked: that the lists are ascending (nothing here needs it) and that an index is below the training rows (no index is
+ * used as an address here). */
+int vf_umap_smooth_knn_query(const int32_t* idx, int64_t ld_idx, const float* dist, int64_t ld_dist, int64_t Rq, int m,
+                             float mean_dist, float* sigma, float* strength, int64_t ld_strength, void* stream);
+
+/* The start of every query (added under ABI 13): the mean of its neighbours' positions weighted by the strengths, umap-learn's
+ * init_transform without its special case for a weight of exactly 1.
+ * Arguments:
+ *   idx       int32 [Rq, >= m], rows ld_idx apart;  strength  fp32 [Rq, >= m], rows ld_strength apart (what
+ *             vf_umap_smooth_knn_query wrote);  Rq, m  as there;
+ *   Y         fp32 [R, >= dim], rows ldy apart: the fitted embedding;  R  training rows;  dim  coordinates, 1 .. VF_UMAP_MAX_DIM;
+ *   Yq        fp32 [Rq, >= dim], rows ldq apart: the queries' positions.
+ * Write set, exactly: Yq[i * ldq + c] for 0 <= i < Rq, 0 <= c < dim.  idx, strength and Y are only read; Y only at rows an index
+ * names.
+ * Arithmetic, per row, in fp32, every operation rounded once: an entry whose index is outside [0, R) is SKIPPED in both sums
+ * (an absent entry's index is negative, or its strength is +0);  S = the sum of the other entries' strengths, t ascending from
+ * +0.0f;  Yq[i, c] = the sum, t ascending from +0.0f, of (strength[i, t] / S) * Y[idx[i, t], c]: the quotient is rounded, then
+ * the product, then the sum.  S == 0 (no usable neighbour) makes the row a quiet NaN: this row cannot be placed.  One wavefront
+ * per row, one lane per entry; the sums walk the lanes in order.
+ * Non-finite operands: follow IEEE through the expression: a NaN strength or a NaN coordinate of a neighbour makes the row's
+ * coordinate NaN.
+ * Refused before anything is launched (VF_ERR_INVALID_ARG, the argument named in vf_last_error()): a null idx, strength, Y or
+ * Yq; any of the four not 4-byte aligned; Y == Yq; m outside 1 .. VF_UMAP_TRANSFORM_MAX_M; Rq < 0; Rq > VF_UMAP_MAX_R; R < 0;
+ * R > VF_UMAP_MAX_R; dim outside 1 .. VF_UMAP_MAX_DIM; ld_idx or ld_strength < m; ldy or ldq < dim.  Rq == 0 is VF_OK with
+ * nothing launched.
+ * Not checked: that Y and Yq do not overlap beyond equality. */
+int vf_umap_init_transform(const int32_t* idx, int64_t ld_idx, const float* strength, int64_t ld_strength, int64_t Rq, int m,
+                           const float* Y, int64_t ldy, int64_t R, int dim, float* Yq, int64_t ldq, void* stream);
+
+/* The epochs [epoch_begin, epoch_end) of the layout of the queries (added under ABI 13), IN PLACE on Yq; the training points
+ * Y stand still and are never written.  The epochs run inside the kernel, at most VF_UMAP_TRANSFORM_EPOCHS_PER_LAUNCH per
+ * launch, from a loop inside the entry.  A query reads only itself and Y, so ANY SPLIT of the epochs over calls or launches,
+ * and any split of the rows over calls that keep first_row + i, gives the same bits as one call.
+ * Arguments:
+ *   idx          int32 [Rq, >= m], rows ld_idx apart: the training neighbours;  samples  int32 [Rq, >= m], rows ld_samples
+ *                apart: how often entry (i, t) is drawn in N epochs, 0 .. N (manifold.py: floor(fl(fl(strength / rowmax) * N)));
+ *   Rq, m        as in vf_umap_smooth_knn_query;  first_row  the number of query row 0 in the hash: row i is first_row + i;
+ *   Y            fp32 [R, >= dim], rows ldy apart;  R  training rows;  dim  1 .. VF_UMAP_MAX_DIM;
+ *   Yq           fp32 [Rq, >= dim], rows ldq apart: read, then written;
+ *   epoch_begin, epoch_end, N   0 <= epoch_begin <= epoch_end <= N;
+ *   a, b         the curve 1 / (1 + a * x^(2b));  gamma  the repulsion strength;  learning_rate  THE FIT'S: the entry divides
+ *                it by 4 (umap-learn's transform);  negative_sample_rate  repulsions per drawn entry, >= 0;  seed  of the
+ *                negative vertices, its low 32 bits.
+ * Write set, exactly: Yq[i * ldq + c] for 0 <= i < Rq, 0 <= c < dim.  Y, idx and samples are only read: idx and samples at
+ * [i, t] with t < m, Y at the rows an index in [0, R) or a negative vertex names.
+ * Arithmetic: query i starts from y = Yq[i] and in every epoch n = epoch_begin .. epoch_end - 1 walks its entries in order,
+ * s = 0 .. m - 1.  Entry (i, s), to j = idx[i, s], is DUE iff
+ *   floor((n + 1) * samples[i, s] / N) > floor(n * samples[i, s] / N)      in 64-bit integers,
+ * which draws it exactly samples[i, s] times in N epochs and needs no state.  With
+ * alpha = fl(learning_rate / 4) * (1 - n / N) in fp32 and clip(v) = v > 4 ? 4 : (v < -4 ? -4 : v), a due entry does, in this
+ * order:
+ *   1. attraction:  d2 = sum_c (y[c] - Y[j][c])^2 (c ascending);  g = d2 > 0 ? ((-2 * a * b) * (p / d2)) / (a * p + 1) : 0 with
+ *      p = pow(d2, b);  y[c] += alpha * clip(g * (y[c] - Y[j][c]));
+ *   2. for p_ = 0 .. negative_sample_rate - 1:  k = (uint64(h) * R) >> 32, R the TRAINING rows, with
+ *        h = mix(mix(mix(mix(mix(seed + 0x9E3779B9) ^ n) ^ (first_row + i)) ^ s) ^ p_),   all in uint32, and
+ *        mix(x): x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16;
+ *      d2 as above against Y[k];  no move if d2 == 0;  otherwise
+ *      g = ((2 * gamma) * b) / ((0.001 + d2) * (a * pow(d2, b) + 1)) and y[c] += alpha * clip(g * (y[c] - Y[k][c])).
+ * There is no step 3: the mirrored entry belongs to a training vertex, and training vertices do not move.  After the last epoch
+ * Yq[i] = y.  One wavefront per query: lane t holds entry t and Y[idx[i, t]] for the whole launch, every lane holds y.
+ * Non-finite operands: follow IEEE: a NaN coordinate of a query keeps that row NaN (clip passes a NaN) and touches no other
+ * row; a NaN training row makes NaN every query that is drawn to it or repelled from it.  Finite positions stay finite: every
+ * move is at most 4 * alpha per coordinate.
+ * Refused before anything is launched (VF_ERR_INVALID_ARG, the argument named in vf_last_error()): a null idx, samples, Y or
+ * Yq; any of the four not 4-byte aligned; Y == Yq; m outside 1 .. VF_UMAP_TRANSFORM_MAX_M; Rq < 0; Rq > VF_UMAP_MAX_R;
+ * first_row < 0; first_row + Rq > 2^32; R < 0; R > VF_UMAP_MAX_R; R < 1 when Rq > 0 and an epoch is asked for; dim outside
+ * 1 .. VF_UMAP_MAX_DIM; ld_idx or ld_samples < m; ldy or ldq < dim; N < 1; epoch_begin < 0; epoch_begin > epoch_end;
+ * epoch_end > N; negative_sample_rate < 0 or above 2^20 (the flat draw number of an epoch, up to 64 times the rate, is an int).
+ * Rq == 0 or an empty epoch range is VF_OK with nothing launched.
+ * Not checked (the caller guarantees): Y and Yq do not overlap beyond equality, samples are in 0 .. N.  Input that is not valid
+ * stays inside the buffers: an entry whose idx is outside [0, R) or whose samples are outside 1 .. N is never due, and its Y
+ * row is not read. */
+int vf_umap_layout_transform(const int32_t* idx, int64_t ld_idx, const int32_t* samples, int64_t ld_samples, int64_t Rq, int m,
+                             int64_t first_row, const float* Y, int64_t ldy, int64_t R, int dim, float* Yq, int64_t ldq,
+                             int epoch_begin, int epoch_end, int N, float a, float b, float gamma, float learning_rate,
+                             int negative_sample_rate, int64_t seed, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* VF_HIP_UMAP_TRANSFORM_H */

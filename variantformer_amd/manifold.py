@@ -19,11 +19,21 @@ are read at epoch-start positions (umap-learn reads and writes them concurrently
 negative_sample_rate repulsions (umap-learn keeps a float schedule).  init is "pca", "random", an array or a callable
 f(graph, n_components, seed) -> positions; umap-learn's default start is init=spectral_init (the string "spectral" stays refused
 and names it).  On a disconnected graph spectral_init falls back to the random initialisation with a warning: umap-learn's
-per-component layout is out of scope.  transform() of new points is out of scope too.  There is no CPU path: without
+per-component layout is out of scope.  There is no CPU path: without
 a GPU the calls raise, after their arguments have been checked.  scipy, umap-learn, numba and pynndescent are not imported.
+
+  fit(x, ...)                      umap(x, ...) kept as a UMAPModel: the embedding, the standardised rows, the fit's arguments;
+  UMAPModel.transform(queries)     new rows placed in the fitted embedding, which stands still (transform(model, queries) is the
+                                   same as a function); UMAPModel.state() / UMAPModel.from_state(dict) store and restore a model.
+
+The transform runs through three entries of include/vf_hip_umap_transform.h: ops.umap_smooth_knn_query (the strengths
+of a query's training neighbours), ops.umap_init_transform (its start among them) and ops.umap_layout_transform (all its epochs in
+one kernel: a query depends on nothing that moves except itself).  A query's result depends on that row, the model, the epoch
+count and its row number alone, so a cohort can be transformed in chunks, bit for bit.
 """
 from __future__ import annotations
 
+import contextvars
 import warnings
 
 import numpy as np
@@ -119,13 +129,19 @@ def _check_graph_lists(indices, distances):
 
 
 # ---- the fuzzy simplicial set ------------------------------------------------------------------------------------------------------
+def _mean_dist(idx: torch.Tensor, dist: torch.Tensor) -> float:
+    """The fp64 mean of the present distances of a k-NN graph, 0 without one: the floor of sigma where rho == 0."""
+    listed = (idx >= 0) & torch.isfinite(dist)
+    return float(dist[listed].to(torch.float64).mean()) if bool(listed.any()) else 0.0
+
+
 def _fuzzy_graph(idx: torch.Tensor, dist: torch.Tensor):
     R, m = idx.shape
     dev = idx.device
     listed = (idx >= 0) & torch.isfinite(dist)                          # the header's "present"
     if bool((idx >= R).any()):
         raise ValueError(f"indices must name rows below {R}")
-    mean_dist = float(dist[listed].to(torch.float64).mean()) if bool(listed.any()) else 0.0
+    mean_dist = _mean_dist(idx, dist)
     rho = torch.empty(R, dtype=torch.float32, device=dev)
     sigma = torch.empty(R, dtype=torch.float32, device=dev)
     strength = torch.empty((R, m), dtype=torch.float32, device=dev)
@@ -518,7 +534,8 @@ def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correla
     f(graph, n_components, seed) -> positions [R, n_components] (numpy or torch; graph = (rowptr, col, w), the device tensors of
     the fuzzy graph; a result of another shape is refused); every init is rescaled per coordinate to [0, 10] and no noise is
     added.  init=manifold.spectral_init is umap-learn's default spectral start (the string "spectral" is refused and names it).
-    transform() of new points is out of scope.  seed also fixes the negative samples: the result is a function of the arguments, bit for bit.
+    New points are placed in a finished embedding by fit(x, ...).transform(queries): fit takes these arguments and keeps what a
+    transform needs.  seed also fixes the negative samples: the result is a function of the arguments, bit for bit.
     Differences from umap-learn, deliberate: other vertices are read where they stood when the epoch began, and
     every drawn edge gets exactly negative_sample_rate repulsions."""
     neighbors._check_matrix(x, "x")
@@ -558,4 +575,178 @@ def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correla
     else:
         y = _tensor(init, torch.float32)
     y = _layout(rowptr, col, w, rescale(y).contiguous(), n_epochs, a, b, gamma, learning_rate, negative_sample_rate, seed)
+    fitted = _FITTED.get()
+    if fitted is not None:                                                # fit() is asking: what a transform needs beside the embedding
+        fitted.update(rows=t, embedding=y, mean_dist=_mean_dist(idx, dist), n_neighbors=n_neighbors, metric=metric, a=a, b=b,
+                      n_epochs=n_epochs, seed=seed, negative_sample_rate=negative_sample_rate, repulsion_strength=gamma,
+                      learning_rate=learning_rate)
     return neighbors._back(x, y)[0]
+
+
+# ---- a fitted model and the transform of new rows ------------------------------------------------------------------------------------
+_FITTED: contextvars.ContextVar = contextvars.ContextVar("variantformer_amd_manifold_fitted", default=None)
+QUERIES_MAX = 1 << 24                      # VF_UMAP_MAX_R
+_STATE_SCALARS = ("n_neighbors", "metric", "a", "b", "n_epochs", "seed", "negative_sample_rate", "repulsion_strength", "learning_rate",
+                  "mean_dist")
+
+
+def transform_samples(strength: torch.Tensor, n_epochs: int) -> torch.Tensor:
+    """int32 like strength: how often each entry of a query's list is drawn in n_epochs epochs,
+    floor(fl(fl(strength / rowmax) * n_epochs)) in individually rounded fp32 with rowmax the ROW's largest strength (umap-learn
+    divides by the batch's: DESIGN.md 5j); 0 in a row whose largest strength is 0."""
+    if strength.numel() == 0:
+        return torch.zeros(strength.shape, dtype=torch.int32, device=strength.device)
+    rowmax = strength.amax(1, keepdim=True)
+    ratio = torch.where(rowmax > 0, strength / rowmax, torch.zeros_like(strength))
+    return torch.floor(ratio * torch.tensor(float(n_epochs), dtype=torch.float32, device=strength.device)).clamp_(0, n_epochs).to(torch.int32)
+
+
+class UMAPModel:
+    """A fitted UMAP: what manifold.fit returns and UMAPModel.from_state restores.  Attributes: `embedding` fp32
+    [rows, n_components] (of the type of the fitted x), `rows`, `n_components`, `n_neighbors`, `metric`, `a`, `b`, `n_epochs`,
+    `seed`, `negative_sample_rate`, `repulsion_strength`, `learning_rate` (all as the fit used them) and `mean_dist`, the fp64
+    mean of the fit's present k-NN distances.  The model also keeps the STANDARDISED training rows (zero mean for a correlation,
+    unit norm), on the device once a transform has run, so that a transform standardises only its queries."""
+
+    def __init__(self, embedding, *, z=None, x=None, n_neighbors, metric, a, b, n_epochs, seed, negative_sample_rate, repulsion_strength,
+                 learning_rate, mean_dist):
+        if not isinstance(embedding, (np.ndarray, torch.Tensor)):
+            raise TypeError(f"embedding must be a numpy array or a torch tensor, not {type(embedding).__name__}")
+        if embedding.ndim != 2 or not 1 <= embedding.shape[1] <= DIM_MAX:
+            raise ValueError(f"embedding must be positions [rows, 1 .. {DIM_MAX}], not {tuple(embedding.shape)}")
+        rows = z if z is not None else x
+        if rows is None:
+            raise ValueError("a model needs its training rows: `z` (standardised, as state() returns them) or `x` (as fitted)")
+        neighbors._check_matrix(rows, "z" if z is not None else "x")
+        if rows.shape[0] != embedding.shape[0]:
+            raise ValueError(f"embedding has {embedding.shape[0]} rows, the training rows are {rows.shape[0]}")
+        if not 1 <= rows.shape[0] <= 1 << 24:
+            raise ValueError(f"a model holds 1 .. 2^24 training rows, not {rows.shape[0]}")
+        if metric not in neighbors.METRICS:
+            raise ValueError(f"metric must be one of {neighbors.METRICS}, not {metric!r}")
+        self.embedding = embedding
+        self.rows, self.columns, self.n_components = int(rows.shape[0]), int(rows.shape[1]), int(embedding.shape[1])
+        self.metric = str(metric)
+        self.n_neighbors = _int_in(n_neighbors, "n_neighbors", 1, N_NEIGHBORS_MAX)
+        (self.n_epochs, self.a, self.b, self.repulsion_strength, self.learning_rate, self.negative_sample_rate, self.seed) = \
+            _check_layout_args(n_epochs, a, b, repulsion_strength, learning_rate, negative_sample_rate, seed)
+        if isinstance(mean_dist, bool) or not isinstance(mean_dist, (int, float, np.integer, np.floating)):
+            raise ValueError(f"mean_dist must be a number, not {mean_dist!r}")
+        self.mean_dist = float(mean_dist)
+        self._z, self._standardised = rows, z is not None
+        self._y = None
+
+    # -- persistence
+    def state(self) -> dict:
+        """Everything a transform needs, as numpy arrays and scalars (np.savez(path, **model.state()) stores it):
+        `embedding` fp32 [rows, n_components], `z` fp32 [rows, columns] -- the standardised training rows, bit for bit what the
+        transform multiplies by --, and the scalars.  A model restored with from_state transforms to the same bits."""
+        if not self._standardised:
+            self._on_device()
+
+        def host(t):
+            return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)
+        out = {"embedding": host(self.embedding if self._y is None else self._y), "z": host(self._z)}
+        out.update({name: getattr(self, name) for name in _STATE_SCALARS})
+        return out
+
+    @classmethod
+    def from_state(cls, state) -> "UMAPModel":
+        """The model of a state(): a dict (or an opened .npz) with `embedding` [rows, 1 .. 8], the training rows -- `z`,
+        standardised as state() returns them and used as they are, or else `x`, raw rows [rows, columns] that are standardised
+        for `metric` on the device (NaN -> 0 first, as in a fit) -- and the scalars n_neighbors (1 .. 64: the training rows a
+        query is attached to), metric, a, b, n_epochs, seed, negative_sample_rate, repulsion_strength, learning_rate, mean_dist.
+        Any embedding of the training rows is accepted, not only a fit's.  Nothing touches the device before a transform."""
+        missing = [k for k in ("embedding",) + _STATE_SCALARS if k not in state]
+        if missing or ("z" not in state and "x" not in state):
+            raise ValueError(f"state lacks {missing + ([] if 'z' in state or 'x' in state else ['z (or x)'])}")
+
+        def scalar(v):
+            v = v.item() if isinstance(v, np.ndarray) and v.ndim == 0 else v
+            return str(v) if isinstance(v, (str, np.str_)) else v
+        return cls(np.asarray(state["embedding"], dtype=np.float32), z=np.asarray(state["z"], dtype=np.float32) if "z" in state else None,
+                   x=None if "z" in state else np.asarray(state["x"], dtype=np.float32), **{k: scalar(state[k]) for k in _STATE_SCALARS})
+
+    def _on_device(self):
+        """The standardised training rows and the embedding as contiguous fp32 tensors on the device, made once."""
+        _need_gpu()
+        if not self._standardised:
+            self._z, self._standardised = neighbors.standardize(self._z, self.metric, True)[0], True
+        if not (isinstance(self._z, torch.Tensor) and self._z.is_cuda and self._z.is_contiguous()):
+            self._z = _tensor(self._z, torch.float32).contiguous()
+        if self._y is None:
+            self._y = _tensor(self.embedding, torch.float32).contiguous()
+        return self._z, self._y
+
+    # -- the transform
+    def transform(self, queries, n_epochs=None, first_row: int = 0):
+        """Place new rows in the fitted embedding, which does not move: fp32 [Rq, n_components] of the type of `queries`
+        [Rq, columns of the fit] (umap-learn's transform).  Each query is attached to its n_neighbors nearest
+        TRAINING rows (neighbors.knn(x, n_neighbors, metric, queries=queries), bit for bit), gets membership strengths with
+        rho = 0 and the model's mean distance as the floor of sigma, starts at the strength-weighted mean of those rows'
+        positions and then runs n_epochs epochs of the layout (None: 100 for up to 10 000 queries, else 30) at a quarter of the
+        fit's learning rate, attracted to its neighbours and repelled from hashed training rows.
+
+        A query's coordinates are a function of that row, the model, n_epochs and its row number first_row + i alone: a cohort
+        transformed in chunks with first_row equals the cohort transformed at once, bit for bit (with n_epochs given: the default
+        depends on the chunk's size), and adding rows to a batch moves nobody else.  A query without a usable neighbour (every
+        similarity NaN) comes out NaN: this row cannot be placed.  ValueError / TypeError before the device is touched: queries
+        of another column count, n_epochs outside 1 .. 2^31 - 1, a negative first_row or one with first_row + Rq > 2^32, more
+        than 2^24 queries.  No queries give an empty [0, n_components]."""
+        neighbors._check_matrix(queries, "queries")
+        if queries.shape[1] != self.columns:
+            raise ValueError(f"queries have {queries.shape[1]} columns, the model was fitted on {self.columns}")
+        Rq = int(queries.shape[0])
+        if Rq > QUERIES_MAX:
+            raise ValueError(f"queries: at most 2^24 rows per call, not {Rq} (transform in chunks with first_row)")
+        if n_epochs is None:
+            n_epochs = 100 if Rq <= 10000 else 30
+        n_epochs = _int_in(n_epochs, "n_epochs", 1, 2 ** 31 - 1)
+        first_row = _int_in(first_row, "first_row", 0, 2 ** 32 - Rq)
+        if Rq == 0:
+            empty = np.zeros((0, self.n_components), dtype=np.float32)
+            return empty if isinstance(queries, np.ndarray) else torch.from_numpy(empty).to(queries.device)
+        z, y = self._on_device()
+        m, dev = self.n_neighbors, z.device
+        zq, _ = neighbors.standardize(queries, self.metric, True)
+        idx = torch.empty((Rq, m), dtype=torch.int32, device=dev)
+        dist = torch.empty((Rq, m), dtype=torch.float32, device=dev)
+        ops.knn_dot(zq, z, m, self_offset=-1, values=dist, indices=idx, family="umap_transform")      # as neighbors.knn does it
+        dist.neg_().add_(1.0)
+        dist.masked_fill_(idx < 0, float("inf"))
+        sigma = torch.empty(Rq, dtype=torch.float32, device=dev)
+        strength = torch.empty((Rq, m), dtype=torch.float32, device=dev)
+        ops.umap_smooth_knn_query(idx, dist, self.mean_dist, sigma=sigma, strength=strength, family="umap_transform")
+        yq = torch.empty((Rq, self.n_components), dtype=torch.float32, device=dev)
+        ops.umap_init_transform(idx, strength, y, out=yq, family="umap_transform")
+        ops.umap_layout_transform(idx, transform_samples(strength, n_epochs), y, yq, epoch_begin=0, epoch_end=n_epochs, n_epochs=n_epochs,
+                                  a=self.a, b=self.b, gamma=self.repulsion_strength, learning_rate=self.learning_rate,
+                                  negative_sample_rate=self.negative_sample_rate, seed=self.seed, first_row=first_row,
+                                  family="umap_transform")
+        return neighbors._back(queries, yq)[0]
+
+
+def fit(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correlation", n_components: int = 2, n_epochs=None,
+        init="pca", seed: int = 42, negative_sample_rate: int = 5, repulsion_strength: float = 1.0, learning_rate: float = 1.0) -> UMAPModel:
+    """umap(x, ...) with the same arguments, kept as a UMAPModel: model.embedding is what umap returns, bit for bit, and
+    model.transform(queries) places new rows in it."""
+    fitted = {}
+    token = _FITTED.set(fitted)
+    try:
+        embedding = umap(x, n_neighbors=n_neighbors, min_dist=min_dist, metric=metric, n_components=n_components, n_epochs=n_epochs,
+                         init=init, seed=seed, negative_sample_rate=negative_sample_rate, repulsion_strength=repulsion_strength,
+                         learning_rate=learning_rate)
+    finally:
+        _FITTED.reset(token)
+    rows, y = fitted.pop("rows"), fitted.pop("embedding")
+    model = UMAPModel(embedding, x=rows, **fitted)
+    model._y = y.contiguous()
+    model._on_device()                                                    # the rows are on the device already: standardise them now
+    return model
+
+
+def transform(model: UMAPModel, queries, n_epochs=None, first_row: int = 0):
+    """model.transform(queries, n_epochs, first_row) as a function."""
+    if not isinstance(model, UMAPModel):
+        raise TypeError(f"model must be a UMAPModel (manifold.fit returns one), not {type(model).__name__}")
+    return model.transform(queries, n_epochs=n_epochs, first_row=first_row)

@@ -1041,6 +1041,100 @@ def umap_layout(rowptr: torch.Tensor, col: torch.Tensor, samples: torch.Tensor, 
     return y0 if epochs % 2 == 0 else y1
 
 
+def umap_smooth_knn_query(idx: torch.Tensor, dist: torch.Tensor, mean_dist: float, *, sigma: torch.Tensor, strength: torch.Tensor,
+                          family: str = ""):
+    """sigma and the directed membership strengths of every QUERY's list of training neighbours (vf_umap_smooth_knn_query,
+    include/vf_hip_umap_transform.h): umap-learn's smooth_knn_dist with local_connectivity - 1 = 0 (rho = +0) and its bipartite
+    compute_membership_strengths.  idx int32 [Rq, m] and dist fp32 [Rq, m] row-strided, what neighbors.knn(x, m, queries=q)
+    returned, only read; m in 1 .. 64; an entry with a negative index or a NaN / infinite distance is absent; an index equal to
+    the row's own number is a training row like any other.  mean_dist: the FIT's mean distance.  sigma fp32 [Rq] contiguous;
+    strength fp32 [Rq, m] row-strided.  The caller owns every buffer and nothing is made here.  Returns (sigma, strength)."""
+    _dev(idx, dist, sigma, strength)
+    assert idx.dtype == torch.int32 and dist.dtype == torch.float32 and strength.dtype == torch.float32 and idx.dim() == 2
+    m = idx.shape[1]
+    assert 1 <= m <= 64, f"m={m} outside 1 .. 64"
+    Rq, ld_idx = _rows(idx, m, "idx")
+    assert dist.shape == idx.shape and strength.shape == idx.shape
+    _, ld_dist = _rows(dist, m, "dist")
+    _, ld_strength = _rows(strength, m, "strength")
+    _vec(sigma, Rq, torch.float32, "sigma")
+
+    def launch():
+        if Rq == 0:
+            return
+        check(_lib.load().vf_umap_smooth_knn_query(idx.data_ptr(), ld_idx, dist.data_ptr(), ld_dist, Rq, m, float(mean_dist),
+                                                   sigma.data_ptr(), strength.data_ptr(), ld_strength, _stream()), "vf_umap_smooth_knn_query")
+    # operations: up to 64 bisection steps of one exp per entry; bytes: the two lists in, strengths and one vector out
+    _run(launch, lambda: ("umap_smooth_knn_query", 65.0 * 4 * Rq * m, 4.0 * (3 * Rq * m + Rq), f"Rq={Rq} m={m}", family or _SCOPE))
+    return sigma, strength
+
+
+def umap_init_transform(idx: torch.Tensor, strength: torch.Tensor, y: torch.Tensor, *, out: torch.Tensor, family: str = ""):
+    """The start of every query: the mean of its training neighbours' positions weighted by strength / (the row's sum of
+    strengths) (vf_umap_init_transform, include/vf_hip_umap_transform.h), in fp32 with every operation rounded once and the sums
+    ascending.  idx int32 [Rq, m] and strength fp32 [Rq, m] row-strided; y fp32 [R, dim] row-strided, the fitted embedding, only
+    read; out fp32 [Rq, dim] row-strided; m in 1 .. 64, dim in 1 .. 8.  An entry whose index is outside [0, R) is skipped; a row
+    without a usable neighbour comes out NaN.  The caller owns every buffer and nothing is made here.  Returns out."""
+    _dev(idx, strength, y, out)
+    assert idx.dtype == torch.int32 and strength.dtype == torch.float32 and idx.dim() == 2 and strength.shape == idx.shape
+    assert y.dtype == torch.float32 and out.dtype == torch.float32 and y.dim() == 2 and out.dim() == 2 and y.shape[1] == out.shape[1]
+    m, dim = idx.shape[1], y.shape[1]
+    assert 1 <= m <= 64, f"m={m} outside 1 .. 64"
+    assert 1 <= dim <= 8, f"dim={dim} outside 1 .. 8"
+    Rq, ld_idx = _rows(idx, m, "idx")
+    _, ld_strength = _rows(strength, m, "strength")
+    R, ldy = _rows(y, dim, "y")
+    rows_out, ldq = _rows(out, dim, "out")
+    assert rows_out == Rq, "out has one row per query"
+
+    def launch():
+        if Rq == 0:
+            return
+        check(_lib.load().vf_umap_init_transform(idx.data_ptr(), ld_idx, strength.data_ptr(), ld_strength, Rq, m, y.data_ptr(), ldy, R,
+                                                 dim, out.data_ptr(), ldq, _stream()), "vf_umap_init_transform")
+    _run(launch, lambda: ("umap_init_transform", 2.0 * Rq * m * (dim + 1), 4.0 * Rq * (m * (2 + dim) + dim), f"Rq={Rq} m={m} dim={dim}",
+                          family or _SCOPE))
+    return out
+
+
+def umap_layout_transform(idx: torch.Tensor, samples: torch.Tensor, y: torch.Tensor, yq: torch.Tensor, *, epoch_begin: int,
+                          epoch_end: int, n_epochs: int, a: float, b: float, gamma: float = 1.0, learning_rate: float = 1.0,
+                          negative_sample_rate: int = 5, seed: int = 42, first_row: int = 0, family: str = ""):
+    """The epochs [epoch_begin, epoch_end) of the layout of the queries IN PLACE on yq, the training points y standing still
+    (vf_umap_layout_transform, include/vf_hip_umap_transform.h): all epochs of a query run inside one kernel, a bounded number
+    per launch from a loop inside the library.  idx int32 [Rq, m] and samples int32 [Rq, m] row-strided, only read; y fp32
+    [R, dim] row-strided, only read; yq fp32 [Rq, dim] row-strided; m in 1 .. 64, dim in 1 .. 8.  learning_rate is the FIT's:
+    the entry divides it by 4.  Row i is vertex first_row + i of the hash, so a query's result depends on its own row, y and
+    that number alone: any split of the epochs, and any split of the rows that keeps the numbers, gives the same bits.  The
+    caller owns every buffer and nothing is made here.  Returns yq."""
+    _dev(idx, samples, y, yq)
+    assert idx.dtype == torch.int32 and samples.dtype == torch.int32 and idx.dim() == 2 and samples.shape == idx.shape
+    assert y.dtype == torch.float32 and yq.dtype == torch.float32 and y.dim() == 2 and yq.dim() == 2 and y.shape[1] == yq.shape[1]
+    m, dim = idx.shape[1], y.shape[1]
+    assert 1 <= m <= 64, f"m={m} outside 1 .. 64"
+    assert 1 <= dim <= 8, f"dim={dim} outside 1 .. 8"
+    Rq, ld_idx = _rows(idx, m, "idx")
+    _, ld_samples = _rows(samples, m, "samples")
+    R, ldy = _rows(y, dim, "y")
+    rows_q, ldq = _rows(yq, dim, "yq")
+    assert rows_q == Rq, "yq has one row per query"
+    epochs = max(int(epoch_end) - int(epoch_begin), 0)
+
+    def launch():
+        if Rq == 0:
+            return
+        check(_lib.load().vf_umap_layout_transform(idx.data_ptr(), ld_idx, samples.data_ptr(), ld_samples, Rq, m, int(first_row),
+                                                   y.data_ptr(), ldy, R, dim, yq.data_ptr(), ldq, int(epoch_begin), int(epoch_end),
+                                                   int(n_epochs), float(a), float(b), float(gamma), float(learning_rate),
+                                                   int(negative_sample_rate), int(seed) & 0xFFFFFFFF, _stream()), "vf_umap_layout_transform")
+    # an upper figure: every entry due in every epoch, 40 operations per move; bytes: the lists and the neighbours' rows once per
+    # launch, a negative vertex's row per repulsion
+    _run(launch, lambda: ("umap_layout_transform", 40.0 * epochs * Rq * m * (1 + int(negative_sample_rate)),
+                          4.0 * Rq * (m * (2 + dim) * -(-epochs // 8) + 2 * dim) + 4.0 * epochs * Rq * m * int(negative_sample_rate) * dim,
+                          f"Rq={Rq} m={m} dim={dim} R={R} epochs={epochs}", family or _SCOPE))
+    return yq
+
+
 def _csr(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor):
     """(vertices, entries) of a CSR graph: rowptr int64 [R + 1], col int32 [nnz], w fp32 [nnz], contiguous."""
     assert rowptr.dim() == 1 and rowptr.shape[0] >= 1, "rowptr: int64 [R + 1]"

@@ -328,7 +328,8 @@ class VCFProcessor:
         leaves = linkage.leaves_list(Z)
         return {"Z": Z, "leaves": leaves, "labels": labels, "ordered_labels": [labels[i] for i in leaves]}
 
-    def expression_umap(self, df, on: str = "predicted_expression", axis: str = "genes", tissue=None, **umap_kwargs):
+    def expression_umap(self, df, on: str = "predicted_expression", axis: str = "genes", tissue=None, return_model: bool = False,
+                        **umap_kwargs):
         """The UMAP picture of a finished prediction, what the reference's vcf2embed notebook draws with
         umap-learn: `df` is what format_output returned; the matrix is neighbors.from_predictions(df, on, axis, tissue) and the
         k-NN graph, the fuzzy simplicial set and the layout run on the device (manifold.umap, which takes `umap_kwargs`:
@@ -339,15 +340,41 @@ class VCFProcessor:
           labels   what names each row of the matrix.
         Rows that are genes (axis="genes" with expression, or embeddings of one `tissue`) also get the columns umap_1 ..
         umap_n of `df`, one number per gene.  Embeddings with tissue=None have (gene, tissue) rows: each gene's cell then holds
-        its tissues' coordinates, fp32 [tissues].  axis="tissues" has no gene rows and adds no column."""
+        its tissues' coordinates, fp32 [tissues].  axis="tissues" has no gene rows and adds no column.
+        return_model=True adds `model`, the manifold.UMAPModel of the fit (the same embedding, bit for bit), which
+        expression_umap_transform takes to place a second prediction in these coordinates."""
         from .. import manifold, neighbors
         m, labels = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
-        coords = manifold.umap(m, **umap_kwargs)
+        model = manifold.fit(m, **umap_kwargs) if return_model else None
+        coords = model.embedding if return_model else manifold.umap(m, **umap_kwargs)
+        self._umap_columns(df, coords, labels, axis)
+        return {"coords": coords, "labels": labels, "model": model} if return_model else {"coords": coords, "labels": labels}
+
+    @staticmethod
+    def _umap_columns(df, coords, labels, axis):
         if axis != "tissues":
             per = len(labels) // len(df)                                 # 1, or the tissues of a (gene, tissue) row set
             for c in range(coords.shape[1]):
                 column = coords[:, c] if per == 1 else list(coords[:, c].reshape(len(df), per))
                 df[f"umap_{c + 1}"] = pd.Series(column, index=df.index, dtype=np.float32 if per == 1 else object)
+
+    def expression_umap_transform(self, model, df, on: str = "predicted_expression", axis: str = "genes", tissue=None, n_epochs=None):
+        """A second prediction in the coordinates of a first: `model` is what
+        expression_umap(first, ..., return_model=True) returned under "model" (or any manifold.UMAPModel), `df` what format_output
+        returned for another individual, cohort or set of alleles.  The matrix is neighbors.from_predictions(df, on, axis, tissue),
+        as in expression_umap, and must have the model's column count (the same tissues, or the same embedding width): another
+        count is refused with both stated.  Every row is placed by model.transform(matrix, n_epochs) among the first frame's
+        points, which do not move, so the two pictures can be compared.  Returns {"coords": fp32 [rows, n_components],
+        "labels"} and adds the columns umap_1 .. umap_n to `df` under expression_umap's rules."""
+        from .. import manifold, neighbors
+        if not isinstance(model, manifold.UMAPModel):
+            raise TypeError(f"model must be a manifold.UMAPModel (expression_umap(..., return_model=True)['model']), not {type(model).__name__}")
+        m, labels = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
+        if m.shape[1] != model.columns:
+            raise ValueError(f"the frame's matrix has {m.shape[1]} columns, the model was fitted on {model.columns}: the two predictions "
+                             f"must cover the same tissues (or embedding width)")
+        coords = model.transform(m, n_epochs=n_epochs)
+        self._umap_columns(df, coords, labels, axis)
         return {"coords": coords, "labels": labels}
 
     def predict_distributed(self, model, checkpoint_path, trainer, vcf_dataset, batch_size: int | None = None, costs=None,
