@@ -8,7 +8,9 @@
   spectral_embedding(graph, n)     the eigenvectors of the graph's normalised Laplacian for its smallest non-trivial eigenvalues, by
                                    Chebyshev-filtered subspace iteration on the device (include/vf_hip_spectral.h, DESIGN.md 5i);
   spectral_init                    that embedding as a callable `init` of umap: umap-learn's default init="spectral";
-  graph_components(graph)          the graph's connected components (labels, count).
+  spectral_init_components         the same start, and on a disconnected graph umap-learn's per-component layout: every component
+                                   solved on its own and placed around a meta position (include/vf_hip_components.h, DESIGN.md 5k);
+  graph_components(graph)          the graph's connected components (labels, count), by a search on the device.
 
 Three entries of include/vf_hip_umap.h do the work: ops.umap_smooth_knn (rho, sigma, directed strengths),
 ops.umap_union (the fuzzy union over the symmetric graph, whose CSR arrays are built here with torch: index plumbing) and
@@ -18,8 +20,8 @@ and can be split at any epoch.  Two deliberate differences from umap-learn follo
 are read at epoch-start positions (umap-learn reads and writes them concurrently), and every drawn edge gets exactly
 negative_sample_rate repulsions (umap-learn keeps a float schedule).  init is "pca", "random", an array or a callable
 f(graph, n_components, seed) -> positions; umap-learn's default start is init=spectral_init (the string "spectral" stays refused
-and names it).  On a disconnected graph spectral_init falls back to the random initialisation with a warning: umap-learn's
-per-component layout is out of scope.  There is no CPU path: without
+and names it).  On a disconnected graph spectral_init falls back to the random initialisation with a warning;
+init=spectral_init_components lays every component out on its own instead, as umap-learn does.  There is no CPU path: without
 a GPU the calls raise, after their arguments have been checked.  scipy, umap-learn, numba and pynndescent are not imported.
 
   fit(x, ...)                      umap(x, ...) kept as a UMAPModel: the embedding, the standardised rows, the fit's arguments;
@@ -293,7 +295,29 @@ def _graph_tensors(graph):
     return (_tensor(graph[0], torch.int64).contiguous(), _tensor(graph[1], torch.int32).contiguous(), _tensor(graph[2], torch.float32).contiguous())
 
 
+COMPONENT_ROUNDS = 8                       # rounds of the component search per call: one scalar is read back per batch
+
+
 def _components(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor):
+    """(labels int32 [R] on the device, count): batches of COMPONENT_ROUNDS rounds of ops.graph_components_rounds from the
+    identity until a batch's last round changed nothing.  The rounds are bounded by R + 1."""
+    R = rowptr.shape[0] - 1
+    dev = rowptr.device
+    parent = torch.arange(R, dtype=torch.int32, device=dev)
+    if R == 0:
+        return parent, 0
+    g, m = torch.empty_like(parent), torch.empty_like(parent)
+    changed = torch.empty(1, dtype=torch.int32, device=dev)
+    for _ in range(-(-(R + 1) // COMPONENT_ROUNDS)):
+        ops.graph_components_rounds(rowptr, col, w, parent, g, m, changed, rounds=COMPONENT_ROUNDS, family="components")
+        if int(changed) == 0:                                             # the batch's one scalar
+            return parent, int((parent == torch.arange(R, dtype=torch.int32, device=dev)).sum())
+    raise RuntimeError(f"graph_components did not settle in {R + 1} rounds")
+
+
+def _components_torch(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor):
+    """_components as torch index plumbing: min-label propagation over the edges with a full pointer-jumping sweep and one
+    scalar read back per round.  A second reference of the search and the baseline of scripts/components_bench.py."""
     R = rowptr.shape[0] - 1
     dev = rowptr.device
     labels = torch.arange(R, dtype=torch.int64, device=dev)
@@ -316,10 +340,10 @@ def _components(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor):
 
 def graph_components(graph):
     """(labels int32 [R], count): the connected components of `graph` -- what fuzzy_graph returned, or (rowptr, col, w) -- by
-    min-label propagation over the edges with pointer jumping, on the device in torch (index plumbing, as the CSR construction
-    is); a round reads one scalar back, rounds are bounded by R.  A label is the smallest vertex of its component; a vertex
-    without an edge is a component of its own; an entry whose weight is not positive is no edge.  labels has the type of the
-    graph's members."""
+    rounds of shortcut, gather and hook-onto-the-parent on the device (ops.graph_components_rounds,
+    include/vf_hip_components.h); a batch of COMPONENT_ROUNDS rounds reads one scalar back, rounds are bounded by R + 1.  A
+    label is the smallest vertex of its component; a vertex without an edge is a component of its own; an entry whose weight
+    is not positive is no edge.  labels has the type of the graph's members."""
     _graph_members(graph)
     _need_gpu()
     labels, count = _components(*_graph_tensors(graph))
@@ -495,9 +519,9 @@ def spectral_embedding(graph, n_components: int = 2, *, block: int = 16, degree:
 def spectral_init(graph, n_components: int, seed: int):
     """An `init` for umap: spectral_embedding(graph, n_components, seed=seed) on a connected graph of at least n_components + 2
     vertices.  Otherwise a RuntimeWarning that names the number of components or the size, and random_init(R, n_components,
-    seed): umap-learn's own fallback when its eigensolver fails (its per-component layout of a disconnected graph is not
-    done here).  Well-separated clusters do disconnect a k-NN graph, so the fallback is no rarity.  Returns a tensor on the
-    device."""
+    seed): umap-learn's own fallback when its eigensolver fails (its per-component layout of a disconnected graph is
+    spectral_init_components).  Well-separated clusters do disconnect a k-NN graph, so the fallback is no rarity.  Returns a
+    tensor on the device."""
     R = _graph_members(graph)
     k, _, _, _, _, seed = _check_spectral_args(n_components, SPECTRAL_BLOCK_MAX, 40, 1e-4, 50, seed)
     _need_gpu()
@@ -514,6 +538,153 @@ def spectral_init(graph, n_components: int, seed: int):
     return _spectral(rowptr, col, w, deg, dinv, k, 16, 40, 1e-4, 50, seed)[0]
 
 
+# ---- the spectral start of a disconnected graph --------------------------------------------------------------------------------------
+COMPONENTS_MAX = 2048                      # more components than this take the random fallback: the solver loop is the host's
+
+
+def meta_positions(count: int, dim: int, centroids=None, metric: str = "correlation") -> np.ndarray:
+    """fp64 [count, dim]: where umap-learn's multi_component_layout puts `count` components, in label order, on the host.
+    count <= 2 dim: the rows of [I_k | 0] and then of -[I_k | 0] with k = ceil(count / 2), cut to count.  Otherwise the spectral
+    embedding of the components' `centroids` [count, d]: the rows standardised for `metric` (a correlation centres them, a
+    cosine does not; a row without spread becomes 0), D = 1 - z z^T with a zero diagonal, the affinity A = exp(-D^2) with its
+    diagonal dropped, the eigenvectors 2 .. dim + 1 of I - D_A^-1/2 A D_A^-1/2 (numpy's eigh) scaled by D_A^-1/2, every one
+    signed so that its largest-magnitude component is positive (the solver's rule), all divided by the largest magnitude
+    overall: scikit-learn's SpectralEmbedding(affinity="precomputed") up to sign and a scale per column.  umap-learn divides
+    by the signed maximum instead."""
+    if count <= 2 * dim:
+        k = -(-count // 2)
+        base = np.zeros((k, dim), dtype=np.float64)
+        base[np.arange(k), np.arange(k)] = 1.0
+        return np.concatenate((base, -base))[:count]
+    if centroids is None:
+        raise ValueError(f"{count} components are more than 2 n_components = {2 * dim}: their meta positions need the data, pass `rows`")
+    z = np.array(centroids, dtype=np.float64)
+    if metric == "correlation":
+        z = z - z.mean(1, keepdims=True)
+    norm = np.sqrt((z * z).sum(1, keepdims=True))
+    z = np.where(norm > 0, z / np.where(norm > 0, norm, 1.0), 0.0)
+    D = 1.0 - z @ z.T
+    np.fill_diagonal(D, 0.0)
+    A = np.exp(-D * D)
+    np.fill_diagonal(A, 0.0)
+    dinv = 1.0 / np.sqrt(A.sum(1))
+    L = np.eye(count) - A * np.outer(dinv, dinv)
+    _, vec = np.linalg.eigh((L + L.T) / 2.0)
+    y = vec[:, 1:dim + 1] * dinv[:, None]
+    big = np.abs(y).argmax(0)
+    y = y * np.where(y[big, np.arange(dim)] < 0, -1.0, 1.0)[None, :]
+    return y / np.abs(y).max()
+
+
+def data_ranges(meta: np.ndarray) -> np.ndarray:
+    """fp64 [count]: half the smallest positive Euclidean distance from each meta position to another (+Inf without one)."""
+    d2 = np.zeros((meta.shape[0], meta.shape[0]), dtype=np.float64)
+    for c in range(meta.shape[1]):
+        d2 += (meta[:, None, c] - meta[None, :, c]) ** 2
+    d = np.sqrt(d2)
+    return np.where(d > 0, d, np.inf).min(1) / 2.0
+
+
+def _random_fallback(count: int, why: str, R: int, k: int, seed: int, device):
+    warnings.warn(f"spectral_init_components: the graph has {count} components ({why}); the random initialisation is used",
+                  RuntimeWarning, stacklevel=3)
+    return random_init(R, k, seed, device)
+
+
+def spectral_init_components(graph, n_components: int, seed: int, rows=None, metric: str = "correlation"):
+    """An `init` for umap that keeps the spectral start on a DISCONNECTED graph: umap-learn's multi_component_layout.  On a
+    connected graph it is spectral_init, bit for bit (the size fallback included).  Otherwise, with C components in label
+    order (a label is the component's smallest vertex) and dim = n_components:
+
+      the graph is renumbered on the device so that every component is a contiguous range of rows with local columns
+      (a stable torch sort of the labels, then ops.csr_components), and its degrees are taken again;
+      meta_positions(C, dim, centroids, metric) places the components: for C > 2 dim from the centroids of `rows` [R, d] (the
+      data the graph was built from; ops.segment_mean_gather on the device, the C x C eigenproblem in fp64 on the host), which
+      are then required -- ValueError that names `rows` without them;
+      data_range(c) is half the smallest positive distance from meta position c to another, rounded to fp32;
+      a component of fewer than max(2 dim, dim + 2) vertices gets (2 u - 1) data_range + meta with u its vertices' OWN rows of
+      random_init(R, dim, seed): counter-based, so no order enters;
+      any other component is solved by the eigensolver with spectral_init's arguments on its slice of the renumbered graph,
+      y, and placed as y * (data_range / max|y|) + meta.
+
+    All of that is fp32 with every operation rounded once, so the result is a function of the arguments, bit for bit.  More
+    than COMPONENTS_MAX = 2048 components, meta positions that do not separate, or a solved component with a vertex whose
+    degree is not positive, take spectral_init's fallback: a RuntimeWarning that states the count, and random_init.  The
+    components are solved one after another from the host (umap-learn loops too).  umap passes `rows` and `metric` itself: the
+    callable carries wants_rows = True.  Returns a tensor on the device."""
+    R = _graph_members(graph)
+    k, _, _, _, _, seed = _check_spectral_args(n_components, SPECTRAL_BLOCK_MAX, 40, 1e-4, 50, seed)
+    if metric not in neighbors.METRICS:
+        raise ValueError(f"metric must be one of {neighbors.METRICS}, not {metric!r}")
+    if rows is not None:
+        neighbors._check_matrix(rows, "rows")
+        if rows.shape[0] != R:
+            raise ValueError(f"rows has {rows.shape[0]} rows, the graph has {R} vertices")
+    _need_gpu()
+    rowptr, col, w = _graph_tensors(graph)
+    dev = rowptr.device
+    if R < k + 2:
+        warnings.warn(f"spectral_init_components: {R} vertices are fewer than n_components + 2 = {k + 2}; the random initialisation is used",
+                      RuntimeWarning, stacklevel=2)
+        return random_init(R, k, seed, dev)
+    deg, dinv = _degrees(rowptr, col, w)
+    labels, count = _components(rowptr, col, w)
+    if count == 1:
+        if not bool((deg > 0).all()):
+            return _random_fallback(count, "and a vertex whose degree is not positive", R, k, seed, dev)
+        return _spectral(rowptr, col, w, deg, dinv, k, 16, 40, 1e-4, 50, seed)[0]
+    if count > COMPONENTS_MAX:
+        return _random_fallback(count, f"more than {COMPONENTS_MAX}", R, k, seed, dev)
+    if count > 2 * k and rows is None:
+        raise ValueError(f"spectral_init_components: {count} components are more than 2 n_components = {2 * k}: their meta positions "
+                         "need the data the graph was built from, pass `rows`")
+    # the graph renumbered by components: index plumbing in torch, the entries in HIP
+    sorted_labels, order64 = torch.sort(labels, stable=True)
+    order = order64.to(torch.int32)
+    rank = torch.empty_like(order)
+    rank[order64] = torch.arange(R, dtype=torch.int32, device=dev)
+    first = torch.ones(R, dtype=torch.bool, device=dev)
+    first[1:] = sorted_labels[1:] != sorted_labels[:-1]
+    comp = (torch.cumsum(first, 0) - 1).to(torch.int32)
+    starts = torch.cat((torch.nonzero(first)[:, 0], torch.tensor([R], dtype=torch.int64, device=dev))).to(torch.int32)
+    rowptr_new = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    rowptr_new[1:] = torch.cumsum((rowptr[1:] - rowptr[:-1])[order64], 0)
+    col_new, w_new = torch.empty_like(col), torch.empty_like(w)
+    ops.csr_components(rowptr, col, w, order, rank, comp, starts, rowptr_new, col_new=col_new, w_new=w_new, family="components")
+    deg_new, dinv_new = _degrees(rowptr_new, col_new, w_new)
+    starts_h = starts.cpu().numpy().astype(np.int64)
+    entries_h = rowptr_new[starts.to(torch.int64)].cpu().numpy()
+    solved = np.diff(starts_h) >= max(2 * k, k + 2)
+    if bool((torch.from_numpy(solved).to(dev)[comp.to(torch.int64)] & ~(deg_new > 0)).any()):
+        return _random_fallback(count, "and a vertex whose degree is not positive", R, k, seed, dev)
+    # where the components go
+    centroids = None
+    if count > 2 * k:
+        x = _tensor(rows, torch.float32)
+        x = x if x.stride(1) == 1 or x.shape[1] <= 1 else x.contiguous()
+        centroids = torch.empty((count, x.shape[1]), dtype=torch.float32, device=dev)
+        centroids = ops.segment_mean_gather(x, order, starts, out=centroids, family="components").cpu().numpy()
+    meta = meta_positions(count, k, centroids, metric)
+    spread = data_ranges(meta)
+    if not (np.isfinite(meta).all() and np.isfinite(spread).all()):
+        return _random_fallback(count, "whose meta positions do not separate", R, k, seed, dev)
+    meta32 = torch.from_numpy(meta.astype(np.float32)).to(dev)
+    spread32 = torch.from_numpy(spread.astype(np.float32)).to(dev)
+    # every vertex as in a small component, from its own row of the hash; the solved components are then written over
+    of_vertex = comp[rank.to(torch.int64)].to(torch.int64)
+    y = (2.0 * random_init(R, k, seed, dev) - 1.0) * spread32[of_vertex][:, None]
+    y = y + meta32[of_vertex]
+    for c in np.nonzero(solved)[0]:
+        s, e, a, b = int(starts_h[c]), int(starts_h[c + 1]), int(entries_h[c]), int(entries_h[c + 1])
+        v = _spectral(rowptr_new[s:e + 1] - a, col_new[a:b], w_new[a:b], deg_new[s:e], dinv_new[s:e], k, 16, 40, 1e-4, 50, seed)[0]
+        placed = v * (spread32[c] / v.abs().max())
+        y[order64[s:e]] = placed + meta32[c]
+    return y
+
+
+spectral_init_components.wants_rows = True
+
+
 # ---- the whole ---------------------------------------------------------------------------------------------------------------------
 def _called_init(init, graph, R: int, n_components: int, seed: int):
     """What the callable `init` returns for (graph, n_components, seed), refused unless it is positions [R, n_components]."""
@@ -522,6 +693,11 @@ def _called_init(init, graph, R: int, n_components: int, seed: int):
         raise ValueError(f"init: the callable must return positions [{R}, {n_components}] (numpy or torch), not "
                          f"{tuple(y.shape) if hasattr(y, 'shape') else type(y).__name__}")
     return y
+
+
+def _with_rows(init, rows, metric: str):
+    """The callable `init` as one of three arguments, with rows= and metric= handed on."""
+    return lambda graph, n_components, seed: init(graph, n_components, seed, rows=rows, metric=metric)
 
 
 def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correlation", n_components: int = 2, n_epochs=None,
@@ -533,7 +709,9 @@ def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correla
     (d >= n_components), "random" (counter-based from `seed`), an array [R, n_components] or a callable
     f(graph, n_components, seed) -> positions [R, n_components] (numpy or torch; graph = (rowptr, col, w), the device tensors of
     the fuzzy graph; a result of another shape is refused); every init is rescaled per coordinate to [0, 10] and no noise is
-    added.  init=manifold.spectral_init is umap-learn's default spectral start (the string "spectral" is refused and names it).
+    added.  init=manifold.spectral_init is umap-learn's default spectral start (the string "spectral" is refused and names it);
+    init=manifold.spectral_init_components keeps that start on a disconnected graph, every component laid out on its own.  A
+    callable that carries wants_rows = True is called as f(graph, n_components, seed, rows=x on the device, metric=metric).
     New points are placed in a finished embedding by fit(x, ...).transform(queries): fit takes these arguments and keeps what a
     transform needs.  seed also fixes the negative samples: the result is a function of the arguments, bit for bit.
     Differences from umap-learn, deliberate: other vertices are read where they stood when the epoch began, and
@@ -571,6 +749,8 @@ def umap(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correla
     if isinstance(init, str):
         y = pca_init(t, n_components) if init == "pca" else random_init(R, n_components, seed, t.device)
     elif callable(init):
+        if getattr(init, "wants_rows", False):                            # it asks for the data: spectral_init_components does
+            init = _with_rows(init, t, metric)
         y = _tensor(_called_init(init, (rowptr, col, w), R, n_components, seed), torch.float32)
     else:
         y = _tensor(init, torch.float32)
@@ -728,8 +908,8 @@ class UMAPModel:
 
 def fit(x, n_neighbors: int = 30, min_dist: float = 0.1, metric: str = "correlation", n_components: int = 2, n_epochs=None,
         init="pca", seed: int = 42, negative_sample_rate: int = 5, repulsion_strength: float = 1.0, learning_rate: float = 1.0) -> UMAPModel:
-    """umap(x, ...) with the same arguments, kept as a UMAPModel: model.embedding is what umap returns, bit for bit, and
-    model.transform(queries) places new rows in it."""
+    """umap(x, ...) with the same arguments (init=spectral_init_components among them: umap hands it the rows), kept as a
+    UMAPModel: model.embedding is what umap returns, bit for bit, and model.transform(queries) places new rows in it."""
     fitted = {}
     token = _FITTED.set(fitted)
     try:

@@ -1240,6 +1240,92 @@ def tall_mul(x: torch.Tensor, t: torch.Tensor, *, out: torch.Tensor, family: str
     return out
 
 
+def graph_components_rounds(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, parent: torch.Tensor, g: torch.Tensor,
+                            m: torch.Tensor, changed: torch.Tensor, *, rounds: int, family: str = ""):
+    """`rounds` rounds of the component search over a CSR graph (vf_graph_components_rounds, include/vf_hip_components.h):
+    shortcut g = P[P], every row's minimum over its neighbours' g, and that minimum hooked onto the row and onto its parent
+    with an atomic integer minimum, three launches per round from a loop inside the library.  parent int32 [R] is the state
+    (the caller starts it as the identity; 0 <= parent[i] <= i), g and m int32 [R] are work vectors, changed int32 [1] is 1
+    if the last round run lowered a parent and 0 if not (untouched with rounds == 0); three distinct buffers.  An entry is an
+    edge only if w > 0 and 0 <= col < R.  A settled state is a fixed point; on a graph of symmetric structure it is
+    parent[i] = the smallest vertex of i's component.  The caller owns every buffer, nothing is made here and nothing is read
+    back.  Returns parent."""
+    _dev(rowptr, col, w, parent, g, m, changed)
+    R, nnz = _csr(rowptr, col, w)
+    _vec(parent, R, torch.int32, "parent")
+    _vec(g, R, torch.int32, "g")
+    _vec(m, R, torch.int32, "m")
+    _vec(changed, 1, torch.int32, "changed")
+    rounds = int(rounds)
+    assert rounds >= 0, f"rounds={rounds} must not be negative"
+
+    def launch():
+        if R == 0 or rounds == 0:
+            return
+        check(_lib.load().vf_graph_components_rounds(rowptr.data_ptr(), col.data_ptr(), w.data_ptr(), nnz, R, parent.data_ptr(), g.data_ptr(),
+                                                     m.data_ptr(), changed.data_ptr(), rounds, _stream()), "vf_graph_components_rounds")
+    # per round: every entry's column, weight and the neighbour's g; the three vectors read and written
+    _run(launch, lambda: ("graph_components_rounds", rounds * (1.0 * nnz + 4.0 * R), rounds * (12.0 * nnz + 8.0 * R + 36.0 * R),
+                          f"R={R} nnz={nnz} rounds={rounds}", family or _SCOPE))
+    return parent
+
+
+def csr_components(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, order: torch.Tensor, rank: torch.Tensor, comp: torch.Tensor,
+                   starts: torch.Tensor, rowptr_new: torch.Tensor, *, col_new: torch.Tensor, w_new: torch.Tensor, family: str = ""):
+    """The CSR graph renumbered by components (vf_csr_components, include/vf_hip_components.h): new row r is old row order[r]
+    with its entries in their order, a column j written as rank[j] - starts[comp[r]] and its weight copied; an entry that is
+    no edge (w <= 0 or NaN, a column outside [0, R) or outside the row's component) as column -1 with weight +0.  order, rank
+    and comp int32 [R], starts int32 [C + 1], rowptr_new int64 [R + 1] (the cumulative permuted row lengths), col_new int32
+    [nnz] and w_new fp32 [nnz], contiguous.  The caller owns every buffer and nothing is made here.  Returns (col_new, w_new)."""
+    _dev(rowptr, col, w, order, rank, comp, starts, rowptr_new, col_new, w_new)
+    R, nnz = _csr(rowptr, col, w)
+    for t, name in ((order, "order"), (rank, "rank"), (comp, "comp")):
+        _vec(t, R, torch.int32, name)
+    assert starts.dim() == 1 and starts.shape[0] >= 1, "starts: int32 [C + 1]"
+    C = starts.shape[0] - 1
+    _vec(starts, C + 1, torch.int32, "starts")
+    _vec(rowptr_new, R + 1, torch.int64, "rowptr_new")
+    _vec(col_new, nnz, torch.int32, "col_new")
+    _vec(w_new, nnz, torch.float32, "w_new")
+    assert R == 0 or 1 <= C <= R, f"C={C} outside 1 .. R={R}"
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_csr_components(rowptr.data_ptr(), col.data_ptr(), w.data_ptr(), nnz, R, order.data_ptr(), rank.data_ptr(),
+                                            comp.data_ptr(), starts.data_ptr(), C, rowptr_new.data_ptr(), col_new.data_ptr(),
+                                            w_new.data_ptr(), _stream()), "vf_csr_components")
+    _run(launch, lambda: ("csr_components", 1.0 * nnz, 20.0 * nnz + 40.0 * R, f"R={R} nnz={nnz} C={C}", family or _SCOPE))
+    return col_new, w_new
+
+
+def segment_mean_gather(x: torch.Tensor, order: torch.Tensor, starts: torch.Tensor, *, out: torch.Tensor, family: str = ""):
+    """out[k] = the mean of the rows x[order[q]] for starts[k] <= q < starts[k + 1] (vf_segment_mean_gather,
+    include/vf_hip_components.h): summed in fp64 in the header's fixed order (four interleaved partials, added in order),
+    divided in fp64 and rounded once to fp32; no atomics.  x fp32 [R, d] and out fp32 [C, d] row-strided, order int32 [R],
+    starts int32 [C + 1] non-decreasing from 0 to R.  A segment without positions gets NaN.  One block per (segment, 64
+    columns).  The caller owns every buffer and nothing is made here.  Returns out."""
+    _dev(x, order, starts, out)
+    assert x.dtype == torch.float32 and out.dtype == torch.float32 and x.dim() == 2 and out.dim() == 2 and x.shape[1] == out.shape[1] >= 1
+    d = x.shape[1]
+    R, ldx = _rows(x, d, "x")
+    assert starts.dim() == 1 and starts.shape[0] >= 1, "starts: int32 [C + 1]"
+    C = starts.shape[0] - 1
+    assert out.shape[0] == C, f"out has {out.shape[0]} rows for {C} segments"
+    ldo = _rows(out, d, "out")[1]
+    _vec(order, R, torch.int32, "order")
+    _vec(starts, C + 1, torch.int32, "starts")
+
+    def launch():
+        if C == 0:
+            return
+        check(_lib.load().vf_segment_mean_gather(x.data_ptr(), ldx, R, d, order.data_ptr(), starts.data_ptr(), C, out.data_ptr(), ldo,
+                                                 _stream()), "vf_segment_mean_gather")
+    _run(launch, lambda: ("segment_mean_gather", 1.0 * R * d, 4.0 * R * d + 4.0 * R * -(-d // 64) + 4.0 * C * d, f"R={R} d={d} C={C}",
+                          family or _SCOPE))
+    return out
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, out_dtype=None, gelu: bool = False,
               eps: float = 1e-5, out: torch.Tensor | None = None) -> torch.Tensor:
     """out_dtype None = the current compute dtype (ops.cdt())."""

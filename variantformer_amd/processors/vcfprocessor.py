@@ -334,7 +334,8 @@ class VCFProcessor:
         umap-learn: `df` is what format_output returned; the matrix is neighbors.from_predictions(df, on, axis, tissue) and the
         k-NN graph, the fuzzy simplicial set and the layout run on the device (manifold.umap, which takes `umap_kwargs`:
         n_neighbors=30, min_dist=0.1, metric="correlation", n_components=2, n_epochs, init="pca", seed=42, ...; init=manifold.spectral_init
-        starts from the eigenvectors of the fuzzy graph's normalised Laplacian, umap-learn's default).  No
+        starts from the eigenvectors of the fuzzy graph's normalised Laplacian, umap-learn's default, DESIGN.md section 5i;
+        init=manifold.spectral_init_components keeps that start where separated clusters disconnect the graph, section 5k).  No
         model and no checkpoint are involved.  Returns a dict:
           coords   fp32 [rows, n_components], one row per row of the matrix;
           labels   what names each row of the matrix.
