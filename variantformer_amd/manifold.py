@@ -32,6 +32,15 @@ The transform runs through three entries of include/vf_hip_umap_transform.h (DES
 of a query's training neighbours), ops.umap_init_transform (its start among them) and ops.umap_layout_transform (all its epochs in
 one kernel: a query depends on nothing that moves except itself).  A query's result depends on that row, the model, the epoch
 count and its row number alone, so a cohort can be transformed in chunks, bit for bit.
+
+  tsne(x, ...)                     t-SNE with the EXACT gradient, pinned stage by stage to scikit-learn's method="exact";
+  tsne_affinities / tsne_descent / tsne_kl   its stages: the joint probabilities P over the k-NN graph, the iterations of the
+                                   descent from given positions (a run can be split), the KL divergence of an embedding.
+
+Four entries of include/vf_hip_tsne.h do that work: ops.tsne_perplexity (scikit-learn's binary search of every
+row's beta), ops.tsne_joint (P = p_cond + p_cond^T over the symmetric CSR graph), ops.tsne_repulsion (one all-pairs pass over the
+embedding, a gather with a stated summation order) and ops.tsne_descent (all iterations of a call from one loop inside the
+library).  scikit-learn is not imported here: tests/tsne_cases.py holds the two together.
 """
 from __future__ import annotations
 
@@ -137,6 +146,23 @@ def _mean_dist(idx: torch.Tensor, dist: torch.Tensor) -> float:
     return float(dist[listed].to(torch.float64).mean()) if bool(listed.any()) else 0.0
 
 
+def _symmetric_csr(idx: torch.Tensor, listed: torch.Tensor):
+    """(rowptr int64 [R + 1], col int32 [nnz]): the symmetric graph of the neighbour lists in CSR: every listed pair in both
+    directions, once, columns ascending within a row; a row that lists itself makes no edge."""
+    R, m = idx.shape
+    dev = idx.device
+    rows = torch.arange(R, dtype=torch.int64, device=dev)[:, None].expand(R, m)
+    edge = listed & (idx != rows)
+    i, j = rows[edge], idx[edge].to(torch.int64)
+    keys = torch.unique(torch.cat((i * R + j, j * R + i)))             # sorted
+    row = torch.div(keys, R, rounding_mode="floor")
+    col = (keys - row * R).to(torch.int32)
+    rowptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    if R:
+        rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=R), 0)
+    return rowptr, col
+
+
 def _fuzzy_graph(idx: torch.Tensor, dist: torch.Tensor):
     R, m = idx.shape
     dev = idx.device
@@ -148,17 +174,7 @@ def _fuzzy_graph(idx: torch.Tensor, dist: torch.Tensor):
     sigma = torch.empty(R, dtype=torch.float32, device=dev)
     strength = torch.empty((R, m), dtype=torch.float32, device=dev)
     ops.umap_smooth_knn(idx, dist, mean_dist, rho=rho, sigma=sigma, strength=strength, family="umap")
-    # the symmetric graph in CSR: every listed pair in both directions, once, columns ascending within a row; a row that lists
-    # itself makes no edge
-    rows = torch.arange(R, dtype=torch.int64, device=dev)[:, None].expand(R, m)
-    edge = listed & (idx != rows)
-    i, j = rows[edge], idx[edge].to(torch.int64)
-    keys = torch.unique(torch.cat((i * R + j, j * R + i)))             # sorted
-    row = torch.div(keys, R, rounding_mode="floor")
-    col = (keys - row * R).to(torch.int32)
-    rowptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
-    if R:
-        rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=R), 0)
+    rowptr, col = _symmetric_csr(idx, listed)
     w = torch.empty(col.shape[0], dtype=torch.float32, device=dev)
     ops.umap_union(idx, strength, rowptr, col, w=w, family="umap")
     return rowptr, col, w, rho, sigma
@@ -930,3 +946,262 @@ def transform(model: UMAPModel, queries, n_epochs=None, first_row: int = 0):
     if not isinstance(model, UMAPModel):
         raise TypeError(f"model must be a UMAPModel (manifold.fit returns one), not {type(model).__name__}")
     return model.transform(queries, n_epochs=n_epochs, first_row=first_row)
+
+
+# ---- t-SNE with the exact gradient -----------------------------------------------------------------------------------------------------
+TSNE_M_MAX = ops.TSNE_MAX_M                # VF_TSNE_MAX_M: the longest neighbour list of the perplexity search
+TSNE_DIM_MAX = ops.TSNE_MAX_DIM            # VF_TSNE_MAX_DIM
+TSNE_EPS = float(np.finfo(np.float64).eps)  # scikit-learn's MACHINE_EPSILON
+TSNE_BLOCKS = 2048                         # blocks the all-pairs pass is cut into at least, where the rows allow: 8 per CU of 256
+TSNE_SPLIT_ROWS = 64                       # a split covers at least this many rows
+TSNE_PANEL_ELEMENTS = 1 << 26              # similarities the panel path of the neighbour lists holds at a time
+
+
+def tsne_splits(R: int) -> int:
+    """How many contiguous ranges of rows the all-pairs pass sums separately at R vertices: a function of R alone, since the
+    result's bits depend on it.  With 256 vertices per block, enough splits for TSNE_BLOCKS blocks, each of at least
+    TSNE_SPLIT_ROWS rows: 29 at 18 000 vertices (71 x 29 = 2059 blocks), 1 up to 64."""
+    tiles = max(-(-R // 256), 1)
+    return max(1, min(-(-TSNE_BLOCKS // tiles), -(-R // TSNE_SPLIT_ROWS)))
+
+
+def _check_tsne_lists(indices, distances, perplexity):
+    for v, name in ((indices, "indices"), (distances, "distances")):
+        if not isinstance(v, (np.ndarray, torch.Tensor)):
+            raise TypeError(f"{name} must be a numpy array or a torch tensor, not {type(v).__name__}")
+        if v.ndim != 2:
+            raise ValueError(f"{name} must be a matrix [rows, neighbours], not {tuple(v.shape)}")
+    if tuple(indices.shape) != tuple(distances.shape):
+        raise ValueError(f"indices {tuple(indices.shape)} and distances {tuple(distances.shape)} must have one shape")
+    if not 1 <= indices.shape[1] <= TSNE_M_MAX:
+        raise ValueError(f"the lists must hold 1 .. {TSNE_M_MAX} neighbours per row (the row itself not among them), not {indices.shape[1]}")
+    if indices.shape[0] > 1 << 24:
+        raise ValueError(f"at most 2^24 rows, not {indices.shape[0]}")
+    perplexity = _number(perplexity, "perplexity", 0.0, True)
+    if perplexity < 1.0 or perplexity >= indices.shape[1]:
+        raise ValueError(f"perplexity must lie in 1 .. the {indices.shape[1]} neighbours of a list (below them), not {perplexity!r}")
+    return perplexity
+
+
+def _tsne_affinities(idx: torch.Tensor, dist: torch.Tensor, perplexity: float):
+    R, m = idx.shape
+    dev = idx.device
+    if bool((idx >= R).any()):
+        raise ValueError(f"indices must name rows below {R}")
+    d2 = dist * dist                                                      # scikit-learn squares a metric that is not Euclidean
+    listed = (idx >= 0) & torch.isfinite(d2)                              # the header's "present", the row itself aside
+    beta = torch.empty(R, dtype=torch.float32, device=dev)
+    p_cond = torch.empty((R, m), dtype=torch.float32, device=dev)
+    ops.tsne_perplexity(idx, d2, perplexity, beta=beta, p_cond=p_cond, family="tsne")
+    rowptr, col = _symmetric_csr(idx, listed)
+    p = torch.empty(col.shape[0], dtype=torch.float32, device=dev)
+    ops.tsne_joint(idx, p_cond, rowptr, col, p=p, family="tsne")
+    # P /= max(sum P, eps): the sum in fp64, one fp32 division per entry (not part of vf_tsne_joint's contract)
+    total = max(float(p.to(torch.float64).sum()), TSNE_EPS) if p.numel() else 1.0
+    p = p / torch.tensor(total, dtype=torch.float64).to(device=dev, dtype=torch.float32)
+    return rowptr, col, p, beta
+
+
+def tsne_affinities(indices, distances, perplexity: float = 30.0):
+    """The joint probabilities P of t-SNE over a k-NN graph: (rowptr int64 [R + 1], col int32 [nnz], p fp32 [nnz], beta fp32 [R]),
+    of the type of `indices`.  indices int [R, m] and distances [R, m]: the m <= 255 OTHER rows nearest to each row and their
+    METRIC distances, as neighbors.knn returns them (1 - s; -1 / +Inf where a row has fewer; a NaN or infinite distance counts
+    as not there).  For a metric that is not Euclidean scikit-learn squares the metric distance before the search; so does this
+    function, with one torch multiply.  Every row's beta is found by scikit-learn's binary search for the given perplexity
+    (1 <= perplexity < m) on the device (ops.tsne_perplexity), p_cond is summed over the symmetric graph (ops.tsne_joint: {i, j}
+    is an edge if either lists the other, stored in both directions, columns ascending, the same bits both ways) and divided
+    by max(sum, eps), the sum in fp64: with m = R - 1 this is scikit-learn's dense P."""
+    perplexity = _check_tsne_lists(indices, distances, perplexity)
+    _need_gpu()
+    out = _tsne_affinities(_tensor(indices, torch.int32).contiguous(), _tensor(distances, torch.float32).contiguous(), perplexity)
+    return neighbors._back(indices, *out)
+
+
+def _tsne_dof(dim: int) -> int:
+    return max(dim - 1, 1)                                                # scikit-learn's degrees_of_freedom
+
+
+def _tsne_run(rowptr, col, p, y, update, gains, iter_begin, iter_end, exaggeration, momentum, learning_rate, min_gain, splits):
+    """Iterations [iter_begin, iter_end) in place on the contiguous device state; returns zsum fp64 [iter_end - iter_begin]."""
+    R, dim = y.shape
+    work = torch.empty(ops.tsne_work_bytes(R, dim, splits) // 8 + 1, dtype=torch.float64, device=y.device)
+    zsum = torch.empty(iter_end - iter_begin, dtype=torch.float64, device=y.device)
+    ops.tsne_descent(rowptr, col, p, y, update, gains, iter_begin=iter_begin, iter_end=iter_end, exaggeration=exaggeration,
+                     momentum=momentum, learning_rate=learning_rate, min_gain=min_gain, dof=_tsne_dof(dim), splits=splits, work=work,
+                     zsum=zsum, family="tsne")
+    return zsum
+
+
+def _check_tsne_graph(graph, y, name: str):
+    _graph_members(graph)
+    if not isinstance(y, (np.ndarray, torch.Tensor)):
+        raise TypeError(f"{name} must be a numpy array or a torch tensor, not {type(y).__name__}")
+    if y.ndim != 2 or not 1 <= y.shape[1] <= TSNE_DIM_MAX:
+        raise ValueError(f"{name} must be positions [rows, 1 .. {TSNE_DIM_MAX}], not {tuple(y.shape)}")
+    if graph[0].shape[0] != y.shape[0] + 1:
+        raise ValueError(f"the graph has {graph[0].shape[0] - 1} rows, {name} has {y.shape[0]}")
+
+
+def tsne_descent(graph, init, iter_begin: int = 0, iter_end: int = 250, exaggeration: float = 1.0, momentum: float = 0.8,
+                 learning_rate: float = 200.0, min_gain: float = 0.01, state=None, return_state: bool = False, splits=None):
+    """The iterations [iter_begin, iter_end) of t-SNE's gradient descent over `graph` -- what tsne_affinities returned, or its
+    first three members (rowptr, col, p) -- from the positions init [R, 1 .. 4], which are not written: scikit-learn's
+    _gradient_descent with its exact _kl_divergence gradient, on the device (ops.tsne_descent).  exaggeration multiplies the
+    attraction (12 in the early phase), momentum and learning_rate are scikit-learn's; the degrees of freedom are
+    max(dim - 1, 1).  state: None for update = 0 and gains = 1 (a fresh _gradient_descent call), or the (update, gains) of an
+    earlier call.  splits: the ranges the all-pairs sum is cut into, default tsne_splits(R).  Returns fp32 [R, dim] of the type
+    of init; return_state=True: (positions, update, gains, zsum) with zsum fp64 [iterations] the normaliser Z of each
+    iteration.  The result depends on the arguments alone: two runs are equal bit for bit, and so is a run split at any
+    iteration with its state carried over."""
+    _check_tsne_graph(graph, init, "init")
+    iter_begin, iter_end = _int_in(iter_begin, "iter_begin", 0, 2 ** 31 - 1), _int_in(iter_end, "iter_end", 0, 2 ** 31 - 1)
+    if iter_begin > iter_end:
+        raise ValueError(f"iter_begin={iter_begin} must not be above iter_end={iter_end}")
+    exaggeration = _number(exaggeration, "exaggeration", 0.0, True)
+    momentum = _number(momentum, "momentum", 0.0, False)
+    learning_rate = _number(learning_rate, "learning_rate", 0.0, True)
+    min_gain = _number(min_gain, "min_gain", 0.0, False)
+    R, dim = init.shape
+    splits = tsne_splits(R) if splits is None else _int_in(splits, "splits", 1, 65535)
+    if state is not None:
+        if not isinstance(state, (tuple, list)) or len(state) != 2 or any(
+                not isinstance(s, (np.ndarray, torch.Tensor)) or tuple(s.shape) != (R, dim) for s in state):
+            raise ValueError(f"state must be (update, gains), each [{R}, {dim}]")
+    _need_gpu()
+    rowptr, col, p = _graph_tensors(graph)
+    y = _tensor(init, torch.float32).contiguous().clone()
+    update = torch.zeros_like(y) if state is None else _tensor(state[0], torch.float32).contiguous().clone()
+    gains = torch.ones_like(y) if state is None else _tensor(state[1], torch.float32).contiguous().clone()
+    zsum = _tsne_run(rowptr, col, p, y, update, gains, iter_begin, iter_end, exaggeration, momentum, learning_rate, min_gain, splits)
+    return neighbors._back(init, y, update, gains, zsum) if return_state else neighbors._back(init, y)[0]
+
+
+def _tsne_kl(rowptr, col, p, y, splits: int) -> float:
+    R, dim = y.shape
+    if R == 0 or p.numel() == 0:
+        return 0.0
+    dof = _tsne_dof(dim)
+    part = torch.empty((splits, R, dim + 1), dtype=torch.float32, device=y.device)
+    ops.tsne_repulsion(y, dof=dof, splits=splits, part=part, family="tsne")
+    z = part[:, :, dim].to(torch.float64).sum()
+    rows = torch.repeat_interleave(torch.arange(R, dtype=torch.int64, device=y.device), rowptr[1:] - rowptr[:-1])
+    y64 = y.to(torch.float64)
+    d2 = ((y64[rows] - y64[col.to(torch.int64)]) ** 2).sum(1)
+    w = (1.0 + d2 / dof) ** (-(dof + 1.0) / 2.0)
+    q = torch.clamp(w / z, min=TSNE_EPS)
+    p64 = p.to(torch.float64)
+    return float((p64 * torch.log(torch.clamp(p64, min=TSNE_EPS) / q)).sum())
+
+
+def tsne_kl(graph, y, splits=None) -> float:
+    """The Kullback-Leibler divergence KL(P || Q) of the embedding y [R, 1 .. 4] over `graph` (tsne_affinities's result):
+    scikit-learn's kl_divergence_ where the graph holds every pair.  Z comes from one all-pairs pass on the device
+    (ops.tsne_repulsion, its column of sums added in fp64), the rest is fp64 torch over the nnz entries:
+    sum_e p_e log(max(p_e, eps) / max(w_e / Z, eps)), every pair counted in both directions as P's normalisation does."""
+    _check_tsne_graph(graph, y, "y")
+    splits = tsne_splits(y.shape[0]) if splits is None else _int_in(splits, "splits", 1, 65535)
+    _need_gpu()
+    return _tsne_kl(*_graph_tensors(graph), _tensor(y, torch.float32).contiguous(), splits)
+
+
+def _knn_panels(t: torch.Tensor, m: int, metric: str):
+    """neighbors.knn's (indices, distances) for lists longer than its 63: ops.pairwise_dot over panels of rows and a stable torch
+    sort, in vf_knn_dot's order (NaN first, descending similarity, ties to the lower column).  One-off plumbing, not a kernel
+    of its own."""
+    z, _ = neighbors.standardize(t, metric, nan_to_zero=False)
+    R = z.shape[0]
+    dev = z.device
+    idx = torch.empty((R, m), dtype=torch.int32, device=dev)
+    dist = torch.empty((R, m), dtype=torch.float32, device=dev)
+    panel = max(1, min(R, TSNE_PANEL_ELEMENTS // max(R, 1)))
+    for r0 in range(0, R, panel):
+        n = min(panel, R - r0)
+        s = torch.empty((n, R), dtype=torch.float32, device=dev)
+        ops.pairwise_dot(z[r0:r0 + n], z, mode=0, out=s, family="tsne")
+        own = torch.arange(n, device=dev)
+        s[own, own + r0] = float("-inf")                                  # the row itself is no neighbour of itself
+        val, order = torch.sort(s, dim=1, descending=True, stable=True)
+        idx[r0:r0 + n] = order[:, :m].to(torch.int32)
+        dist[r0:r0 + n] = 1.0 - val[:, :m]                                # 1 - s: the negation is exact
+    return idx, dist
+
+
+def tsne(x, perplexity: float = 30.0, metric: str = "correlation", n_components: int = 2, n_iter: int = 1000,
+         early_exaggeration: float = 12.0, exaggeration_iter: int = 250, learning_rate="auto", init="pca", seed: int = 42,
+         n_neighbors=None, return_kl: bool = False):
+    """The t-SNE embedding of the rows of x [R, d] (numpy or torch) with the EXACT gradient: fp32 [R, n_components] of the type
+    of x, or (embedding, KL divergence) with return_kl=True.
+
+    The affinities are tsne_affinities of the n_neighbors nearest rows under `metric` (default min(R - 1, int(3 perplexity + 1)),
+    at most 255; perplexity must stay below it): neighbors.knn up to 63 neighbours, and beyond that (the default perplexity's 91
+    among them) lists built from ops.pairwise_dot row panels and a stable torch sort, in the same order.  With
+    n_neighbors = R - 1 P is scikit-learn's dense P.  The descent is scikit-learn's: exaggeration_iter iterations with P
+    multiplied by early_exaggeration at momentum 0.5, then the rest up to n_iter at momentum 0.8, update and gains starting
+    afresh in each phase as its two _gradient_descent calls do; min_gain 0.01; learning_rate "auto" = max(R / early_exaggeration
+    / 4, 50).  Every iteration sums the repulsion over ALL pairs on the device: no Barnes-Hut tree, no interpolation grid.
+    init: "pca" (pca_init, d >= n_components) or "random" (random_init from `seed`), both scaled so that the first column's
+    standard deviation is 1e-4 as scikit-learn scales its PCA start (a start whose first coordinate has no finite spread, as
+    identical rows give under "pca", is refused with a ValueError where scikit-learn would divide by zero); an array [R, n_components], taken as it is; or a callable
+    f(graph, n_components, seed) -> positions as in umap, taken as it is.
+    Differences from scikit-learn, deliberate: the iteration count is fixed (its early stopping on the error's
+    progress and the gradient norm is left out), the arithmetic is fp32 with stated summation orders (its is fp64), and P is
+    sparse unless n_neighbors = R - 1.  The result is a function of the arguments, bit for bit."""
+    neighbors._check_matrix(x, "x")
+    if metric not in neighbors.METRICS:
+        raise ValueError(f"metric must be one of {neighbors.METRICS}, not {metric!r}")
+    n_components = _int_in(n_components, "n_components", 1, TSNE_DIM_MAX)
+    R = x.shape[0]
+    if R < 3 or R > 1 << 24:
+        raise ValueError(f"x must hold 3 .. 2^24 rows, not {R}")
+    perplexity = _number(perplexity, "perplexity", 0.0, True)
+    if n_neighbors is None:
+        n_neighbors = min(R - 1, int(3.0 * perplexity + 1.0))
+    n_neighbors = _int_in(n_neighbors, "n_neighbors", 2, min(R - 1, TSNE_M_MAX))
+    if perplexity < 1.0 or perplexity >= n_neighbors:
+        raise ValueError(f"perplexity must lie in 1 .. n_neighbors={n_neighbors} (below it), not {perplexity!r}")
+    n_iter = _int_in(n_iter, "n_iter", 0, 2 ** 31 - 1)
+    exaggeration_iter = _int_in(exaggeration_iter, "exaggeration_iter", 0, 2 ** 31 - 1)
+    early_exaggeration = _number(early_exaggeration, "early_exaggeration", 0.0, True)
+    if isinstance(learning_rate, str):
+        if learning_rate != "auto":
+            raise ValueError(f"learning_rate must be 'auto' or a positive number, not {learning_rate!r}")
+        learning_rate = max(R / early_exaggeration / 4.0, 50.0)
+    learning_rate = _number(learning_rate, "learning_rate", 0.0, True)
+    seed = _int_in(seed, "seed", 0, 2 ** 32 - 1)
+    if isinstance(init, str):
+        if init not in INITS:
+            raise ValueError(f"init must be one of {INITS}, an array [rows, n_components] or a callable, not {init!r}")
+        if init == "pca" and x.shape[1] < n_components:
+            raise ValueError(f"init='pca' needs at least n_components={n_components} columns, x has {x.shape[1]}")
+    elif callable(init):
+        pass                                                              # its result is checked when it has been called
+    elif not isinstance(init, (np.ndarray, torch.Tensor)) or tuple(init.shape) != (R, n_components):
+        raise ValueError(f"init must be one of {INITS}, a callable or an array [{R}, {n_components}]")
+    t = neighbors._to_device(x, True)
+    y = None
+    if isinstance(init, str):                                             # before the graph: a start without spread is refused early
+        y = pca_init(t, n_components) if init == "pca" else random_init(R, n_components, seed, t.device)
+        spread = float(y[:, 0].std(unbiased=False))
+        if not (np.isfinite(spread) and spread > 0.0):
+            raise ValueError(f"init={init!r}: the start's first coordinate has no finite spread (standard deviation {spread!r}; identical "
+                             "or non-finite rows?), so it cannot be scaled to 1e-4: pass init='random' or an array")
+        y = y / spread * 1e-4
+    if n_neighbors <= N_NEIGHBORS_MAX - 1:
+        idx, dist = neighbors.knn(t, k=n_neighbors, metric=metric)
+    else:
+        idx, dist = _knn_panels(t, n_neighbors, metric)
+    rowptr, col, p, _ = _tsne_affinities(idx, dist, perplexity)
+    if callable(init):
+        y = _tensor(_called_init(init, (rowptr, col, p), R, n_components, seed), torch.float32)
+    elif y is None:
+        y = _tensor(init, torch.float32)
+    y = y.contiguous().clone()
+    splits = tsne_splits(R)
+    early = min(exaggeration_iter, n_iter)
+    for begin, end, exaggeration, momentum in ((0, early, early_exaggeration, 0.5), (early, n_iter, 1.0, 0.8)):
+        if end > begin:
+            _tsne_run(rowptr, col, p, y, torch.zeros_like(y), torch.ones_like(y), begin, end, exaggeration, momentum, learning_rate,
+                      0.01, splits)
+    if return_kl:
+        return neighbors._back(x, y)[0], _tsne_kl(rowptr, col, p, y, splits)
+    return neighbors._back(x, y)[0]

@@ -1041,6 +1041,131 @@ def umap_layout(rowptr: torch.Tensor, col: torch.Tensor, samples: torch.Tensor, 
     return y0 if epochs % 2 == 0 else y1
 
 
+TSNE_MAX_M, TSNE_MAX_DIM, TSNE_Z_BLOCKS = 255, 4, 64      # VF_TSNE_MAX_M, VF_TSNE_MAX_DIM, VF_TSNE_Z_BLOCKS
+
+
+def tsne_work_bytes(R: int, dim: int, splits: int) -> int:
+    """VF_TSNE_WORK_BYTES(R, dim, splits) of include/vf_hip_tsne.h: the bytes of tsne_descent's workspace."""
+    return 8 * TSNE_Z_BLOCKS + 4 * (int(splits) * int(R) * (int(dim) + 1) + int(R) * int(dim))
+
+
+def tsne_perplexity(idx: torch.Tensor, d2: torch.Tensor, perplexity: float, *, beta: torch.Tensor, p_cond: torch.Tensor, family: str = ""):
+    """The conditional probabilities of every row's neighbour list at the given perplexity (vf_tsne_perplexity,
+    include/vf_hip_tsne.h): scikit-learn's _binary_search_perplexity, the row's smallest squared distance subtracted before the
+    exponential.  idx int32 [R, m] and d2 fp32 [R, m] (SQUARED distances) row-strided, only read; m in 1 .. 255; an entry with
+    a negative index, a NaN / infinite distance or idx == the row is left out and gets +0.  1 <= perplexity < m.  beta fp32 [R]
+    contiguous; p_cond fp32 [R, m] row-strided.  The caller owns every buffer and nothing is made here.  Returns (beta, p_cond)."""
+    _dev(idx, d2, beta, p_cond)
+    assert idx.dtype == torch.int32 and d2.dtype == torch.float32 and p_cond.dtype == torch.float32 and idx.dim() == 2
+    m = idx.shape[1]
+    assert 1 <= m <= TSNE_MAX_M, f"m={m} outside 1 .. {TSNE_MAX_M}"
+    R, ld_idx = _rows(idx, m, "idx")
+    assert d2.shape == idx.shape and p_cond.shape == idx.shape
+    _, ld_d2 = _rows(d2, m, "d2")
+    _, ld_p = _rows(p_cond, m, "p_cond")
+    _vec(beta, R, torch.float32, "beta")
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_tsne_perplexity(idx.data_ptr(), ld_idx, d2.data_ptr(), ld_d2, R, m, float(perplexity), beta.data_ptr(),
+                                             p_cond.data_ptr(), ld_p, _stream()), "vf_tsne_perplexity")
+    # operations: up to 100 search steps of one exp, one division and a few more per entry; bytes: the two lists in, P and beta out
+    _run(launch, lambda: ("tsne_perplexity", 100.0 * 8 * R * m, 4.0 * (3 * R * m + R), f"R={R} m={m}", family or _SCOPE))
+    return beta, p_cond
+
+
+def tsne_joint(idx: torch.Tensor, p_cond: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, *, p: torch.Tensor, family: str = ""):
+    """The symmetric sum of the conditional probabilities over the symmetric graph (vf_tsne_joint, include/vf_hip_tsne.h): for
+    every CSR entry (i, j = col[e]) p[e] = a + b with a the p_cond of j in row i's list and b that of i in row j's, +0 where it
+    is not listed; p[i -> j] and p[j -> i] have the same bits.  Not normalised.  idx int32 [R, m] and p_cond fp32 [R, m]
+    row-strided; rowptr int64 [R + 1], col int32 [nnz], p fp32 [nnz] contiguous.  The caller owns every buffer and nothing is
+    made here.  Returns p."""
+    _dev(idx, p_cond, rowptr, col, p)
+    assert idx.dtype == torch.int32 and p_cond.dtype == torch.float32 and idx.dim() == 2 and p_cond.shape == idx.shape
+    m = idx.shape[1]
+    assert 1 <= m <= TSNE_MAX_M, f"m={m} outside 1 .. {TSNE_MAX_M}"
+    R, ld_idx = _rows(idx, m, "idx")
+    _, ld_p = _rows(p_cond, m, "p_cond")
+    nnz = col.shape[0]
+    _vec(rowptr, R + 1, torch.int64, "rowptr")
+    _vec(col, nnz, torch.int32, "col")
+    _vec(p, nnz, torch.float32, "p")
+
+    def launch():
+        if R == 0 or nnz == 0:
+            return
+        check(_lib.load().vf_tsne_joint(idx.data_ptr(), ld_idx, p_cond.data_ptr(), ld_p, R, m, rowptr.data_ptr(), col.data_ptr(), nnz,
+                                        p.data_ptr(), _stream()), "vf_tsne_joint")
+    _run(launch, lambda: ("tsne_joint", 1.0 * nnz, 4.0 * nnz * (2 + m) + 8.0 * R, f"R={R} m={m} nnz={nnz}", family or _SCOPE))
+    return p
+
+
+def tsne_repulsion(y: torch.Tensor, *, dof: int, splits: int, part: torch.Tensor, family: str = ""):
+    """One all-pairs pass of t-SNE's repulsive force (vf_tsne_repulsion, include/vf_hip_tsne.h).  y fp32 [R, dim] row-strided,
+    dim in 1 .. 4, only read; dof in 1 .. 3; part fp32 [splits, R, dim + 1] contiguous: for vertex i and split s, over the rows
+    j != i of the split's contiguous range in ascending order, columns 0 .. dim - 1 get sum w w (y_i - y_j) and column dim
+    gets sum w, w = (1 + d2 / dof)^-((dof + 1) / 2).  No atomic: one result, bit for bit.  The caller owns every buffer and
+    nothing is made here.  Returns part."""
+    _dev(y, part)
+    assert y.dtype == torch.float32 and y.dim() == 2 and part.dtype == torch.float32
+    dim = y.shape[1]
+    assert 1 <= dim <= TSNE_MAX_DIM, f"dim={dim} outside 1 .. {TSNE_MAX_DIM}"
+    R, ld = _rows(y, dim, "y")
+    splits = int(splits)
+    assert part.dim() == 3 and tuple(part.shape) == (splits, R, dim + 1) and (part.numel() == 0 or part.is_contiguous()), \
+        f"part: a contiguous fp32 [{splits}, {R}, {dim + 1}]"
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_tsne_repulsion(y.data_ptr(), ld, R, dim, int(dof), splits, part.data_ptr(), _stream()), "vf_tsne_repulsion")
+    # per pair: the differences, d2, one reciprocal, the weight and dim + 1 accumulations
+    _run(launch, lambda: ("tsne_repulsion", (5.0 * dim + 6) * R * R, 4.0 * (R * dim + splits * R * (dim + 1)),
+                          f"R={R} dim={dim} dof={int(dof)} splits={splits}", family or _SCOPE))
+    return part
+
+
+def tsne_descent(rowptr: torch.Tensor, col: torch.Tensor, p: torch.Tensor, y: torch.Tensor, update: torch.Tensor, gains: torch.Tensor, *,
+                 iter_begin: int, iter_end: int, exaggeration: float, momentum: float, learning_rate: float, min_gain: float = 0.01,
+                 dof: int, splits: int, work: torch.Tensor, zsum: torch.Tensor, family: str = ""):
+    """The iterations [iter_begin, iter_end) of t-SNE's gradient descent with the exact gradient (vf_tsne_descent,
+    include/vf_hip_tsne.h), from one loop inside the library: scikit-learn's _gradient_descent over its _kl_divergence.  rowptr
+    int64 [R + 1], col int32 [nnz], p fp32 [nnz] (normalised) contiguous, only read; y, update, gains fp32 [R, dim] row-strided
+    with one stride, the state, written in place; work a contiguous uint8 / any-dtype tensor of at least
+    tsne_work_bytes(R, dim, splits) bytes; zsum fp64 [iter_end - iter_begin], each iteration's Z.  One result, bit for bit, and
+    [0, 20) equals [0, 7) then [7, 20) on the carried state.  The caller owns every buffer and nothing is made here.  Returns
+    (y, update, gains, zsum)."""
+    _dev(rowptr, col, p, y, update, gains, work, zsum)
+    assert y.dtype == torch.float32 and y.dim() == 2 and update.dtype == torch.float32 and gains.dtype == torch.float32
+    assert update.shape == y.shape and gains.shape == y.shape
+    dim = y.shape[1]
+    assert 1 <= dim <= TSNE_MAX_DIM, f"dim={dim} outside 1 .. {TSNE_MAX_DIM}"
+    R, ld = _rows(y, dim, "y")
+    assert _rows(update, dim, "update")[1] == ld and _rows(gains, dim, "gains")[1] == ld, "y, update and gains have one row stride"
+    nnz = col.shape[0]
+    _vec(rowptr, R + 1, torch.int64, "rowptr")
+    _vec(col, nnz, torch.int32, "col")
+    _vec(p, nnz, torch.float32, "p")
+    iters = int(iter_end) - int(iter_begin)
+    _vec(zsum, max(iters, 0), torch.float64, "zsum")
+    splits = int(splits)
+    assert work.is_contiguous(), "work: a contiguous buffer"
+    work_bytes = work.numel() * work.element_size()
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_tsne_descent(rowptr.data_ptr(), _ptr(col) if nnz else 0, _ptr(p) if nnz else 0, nnz, R, dim, y.data_ptr(),
+                                          update.data_ptr(), gains.data_ptr(), ld, int(iter_begin), int(iter_end), float(exaggeration),
+                                          float(momentum), float(learning_rate), float(min_gain), int(dof), splits, work.data_ptr(),
+                                          work_bytes, zsum.data_ptr() if iters > 0 else 0, _stream()), "vf_tsne_descent")
+    _run(launch, lambda: ("tsne_descent", max(iters, 0) * ((5.0 * dim + 6) * R * R + (5.0 * dim + 6) * nnz),
+                          4.0 * max(iters, 0) * (2 * nnz + 2 * splits * R * (dim + 1) + 8 * R * dim),
+                          f"R={R} dim={dim} nnz={nnz} dof={int(dof)} splits={splits} iters={iters}", family or _SCOPE))
+    return y, update, gains, zsum
+
+
 def umap_smooth_knn_query(idx: torch.Tensor, dist: torch.Tensor, mean_dist: float, *, sigma: torch.Tensor, strength: torch.Tensor,
                           family: str = ""):
     """sigma and the directed membership strengths of every QUERY's list of training neighbours (vf_umap_smooth_knn_query,

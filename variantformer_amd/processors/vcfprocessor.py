@@ -351,13 +351,31 @@ class VCFProcessor:
         self._umap_columns(df, coords, labels, axis)
         return {"coords": coords, "labels": labels, "model": model} if return_model else {"coords": coords, "labels": labels}
 
+    def expression_tsne(self, df, on: str = "predicted_expression", axis: str = "genes", tissue=None, **tsne_kwargs):
+        """The t-SNE picture of a finished prediction, the first of the "alternative methods" the
+        reference's vcf2embed notebook lists as next steps: the twin of expression_umap.  `df` is what format_output returned;
+        the matrix is neighbors.from_predictions(df, on, axis, tissue), and the neighbour lists, the perplexity search and the
+        descent with the exact all-pairs gradient run on the device (manifold.tsne, which takes `tsne_kwargs`: perplexity=30,
+        metric="correlation", n_components=2, n_iter=1000, early_exaggeration=12, exaggeration_iter=250, learning_rate="auto",
+        init="pca", seed=42, n_neighbors=None).  No model and no checkpoint are involved.  Returns a dict:
+          coords   fp32 [rows, n_components], one row per row of the matrix;
+          labels   what names each row of the matrix.
+        The columns tsne_1 .. tsne_n are added to `df` under expression_umap's rules."""
+        from .. import manifold, neighbors
+        if "return_kl" in tsne_kwargs:
+            raise ValueError("expression_tsne returns coordinates: ask manifold.tsne(..., return_kl=True) for the divergence")
+        m, labels = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
+        coords = manifold.tsne(m, **tsne_kwargs)
+        self._umap_columns(df, coords, labels, axis, prefix="tsne")
+        return {"coords": coords, "labels": labels}
+
     @staticmethod
-    def _umap_columns(df, coords, labels, axis):
+    def _umap_columns(df, coords, labels, axis, prefix: str = "umap"):
         if axis != "tissues":
             per = len(labels) // len(df)                                 # 1, or the tissues of a (gene, tissue) row set
             for c in range(coords.shape[1]):
                 column = coords[:, c] if per == 1 else list(coords[:, c].reshape(len(df), per))
-                df[f"umap_{c + 1}"] = pd.Series(column, index=df.index, dtype=np.float32 if per == 1 else object)
+                df[f"{prefix}_{c + 1}"] = pd.Series(column, index=df.index, dtype=np.float32 if per == 1 else object)
 
     def expression_umap_transform(self, model, df, on: str = "predicted_expression", axis: str = "genes", tissue=None, n_epochs=None):
         """A second prediction in the coordinates of a first: `model` is what
