@@ -4,7 +4,8 @@ over the ~18 000 genes for the row order of the heatmap.
 
   ward(D)            Z in scipy's format from a square distance matrix (its upper triangle), numpy or torch;
   ward_of_rows(x)    neighbors.correlation_distance(x) followed by ward, on the device throughout;
-  leaves_list(Z)     the left-to-right leaf order of Z, as scipy.cluster.hierarchy.leaves_list.
+  leaves_list(Z)     the left-to-right leaf order of Z, as scipy.cluster.hierarchy.leaves_list;
+  cut(Z, n_clusters) the flat clusters of Z, the partition of scipy.cluster.hierarchy.cut_tree, on the host.
 
 Ward is a reducible linkage: every pair of mutually nearest clusters belongs to the final tree, so all such pairs merge at once.
 A round is two entries of include/vf_hip_linkage.h: ops.linkage_nearest finds every row's nearest row,
@@ -171,3 +172,44 @@ def leaves_list(Z) -> np.ndarray:
             stack.append(int(right))
             stack.append(int(left))
     return out
+
+
+def cut(Z, n_clusters) -> np.ndarray:
+    """The flat clusters of the tree Z: the partition of scipy.cluster.hierarchy.cut_tree(Z, n_clusters=...) for a monotone Z (a
+    parent never below its children, which ward returns), on the host in plain numpy.  n_clusters: an integer in 1 .. rows, or
+    a list of them.  The first rows - n_clusters merges of Z are applied; the clusters are numbered 0, 1, .. by their lowest
+    row.  Returns int32 [rows], or [rows, len(n_clusters)] for a list: the step between ward / ward_of_rows and labels."""
+    Z = np.asarray(Z)
+    if Z.ndim != 2 or Z.shape[1] != 4 or Z.shape[0] < 1:
+        raise ValueError(f"Z must be a linkage matrix [n - 1, 4], not {tuple(Z.shape)}")
+    n = Z.shape[0] + 1
+    children = Z[:, :2].astype(np.int64)
+    if children.min() < 0 or (children >= n + np.arange(n - 1)[:, None]).any():
+        raise ValueError("Z is no linkage: a row names a cluster that is not made before it")
+    if (np.bincount(children.ravel(), minlength=2 * n - 2) != 1).any():
+        raise ValueError("Z is no linkage: every leaf and every cluster but the last is merged exactly once")
+    if (np.diff(Z[:, 2]) < 0).any():
+        raise ValueError("Z is not monotone: its heights must not fall from one row to the next")
+    many = isinstance(n_clusters, (list, tuple, np.ndarray))
+    wanted = list(n_clusters) if many else [n_clusters]
+    if many and not wanted:
+        raise ValueError("n_clusters must name at least one number of clusters")
+    for c in wanted:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= c <= n:
+            raise ValueError(f"n_clusters must be an integer in 1 .. {n}, not {c!r}")
+    out = np.empty((n, len(wanted)), dtype=np.int32)
+    for col, c in enumerate(wanted):
+        parent = np.arange(2 * n - 1, dtype=np.int64)
+        done = n - int(c)                                                # the merges applied
+        parent[children[:done].ravel()] = np.repeat(n + np.arange(done), 2)
+        while True:                                                       # pointer doubling: every node to the top of its tree
+            up = parent[parent]
+            if np.array_equal(up, parent):
+                break
+            parent = up
+        root = parent[:n]
+        _, first, inverse = np.unique(root, return_index=True, return_inverse=True)
+        rank = np.empty(first.shape[0], dtype=np.int32)
+        rank[np.argsort(first, kind="stable")] = np.arange(first.shape[0], dtype=np.int32)
+        out[:, col] = rank[inverse.reshape(-1)]
+    return out if many else out[:, 0]

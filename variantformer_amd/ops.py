@@ -1166,6 +1166,72 @@ def tsne_descent(rowptr: torch.Tensor, col: torch.Tensor, p: torch.Tensor, y: to
     return y, update, gains, zsum
 
 
+ENRICH_MAX_K, ENRICH_MAX_N = 4096, 1 << 24                # VF_ENRICH_MAX_K, VF_ENRICH_MAX_N
+
+
+def enrich_counts(termptr: torch.Tensor, gene: torch.Tensor, labels: torch.Tensor, k: int, *, count: torch.Tensor, size: torch.Tensor,
+                  family: str = ""):
+    """The overlap of every annotation term with every cluster (vf_enrich_counts, include/vf_hip_enrich.h).  termptr int64
+    [T + 1] and gene int32 [nnz]: the term-major CSR annotation, universe rows; an entry outside [0, G) is skipped.  labels int32
+    [G]: 0 .. k - 1 names a cluster, any other value no cluster.  count int32 [T, k] row-strided: count[t, c] = the entries of
+    term t whose gene has label c; size int32 [T]: the entries of term t inside the universe.  Integers: exact, whatever the
+    order.  The cluster sizes are this call with the one term that lists every gene.  The caller owns every buffer and nothing
+    is made here.  Returns (count, size)."""
+    _dev(termptr, gene, labels, count, size)
+    k = int(k)
+    assert 1 <= k <= ENRICH_MAX_K, f"k={k} outside 1 .. {ENRICH_MAX_K}"
+    assert count.dtype == torch.int32 and count.dim() == 2 and count.shape[1] == k
+    T, ldc = _rows(count, k, "count")
+    nnz, G = gene.shape[0], labels.shape[0]
+    _vec(termptr, T + 1, torch.int64, "termptr")
+    _vec(gene, nnz, torch.int32, "gene")
+    _vec(labels, G, torch.int32, "labels")
+    _vec(size, T, torch.int32, "size")
+
+    def launch():
+        if T == 0:
+            return
+        # G == 0: nothing reads labels, and an empty tensor has no address: `termptr` stands in for it
+        check(_lib.load().vf_enrich_counts(termptr.data_ptr(), _ptr(gene) if nnz else 0, nnz, T, labels.data_ptr() if G else termptr.data_ptr(),
+                                           G, k, count.data_ptr(), ldc, size.data_ptr(), _stream()), "vf_enrich_counts")
+    _run(launch, lambda: ("enrich_counts", 0.0, 4.0 * (2 * nnz + T * (k + 1)) + 8.0 * T, f"T={T} k={k} nnz={nnz} G={G}", family or _SCOPE))
+    return count, size
+
+
+def hypergeom_tail(count: torch.Tensor, size: torch.Tensor, csize: torch.Tensor, N: int, logfact: torch.Tensor, alternative: int, *,
+                   log_p: torch.Tensor, tail: torch.Tensor, steps: torch.Tensor, family: str = ""):
+    """The hypergeometric tail of every (term, cluster) cell (vf_hypergeom_tail, include/vf_hip_enrich.h): for x = count[t, c],
+    K = size[t], n = csize[c] and the universe N, log P[X >= x] (alternative 0: scipy's hypergeom.sf(x - 1, N, K, n)) or
+    log P[X <= x] (alternative 1: hypergeom.cdf).  count int32 [T, k] row-strided, size int32 [T], csize int32 [k]; logfact fp64
+    [N + 1] = lgamma(i + 1), from the host.  log_p and tail fp64 [T, k], steps int32 [T, k], row-strided with ONE stride: the
+    natural log of the tail, the sum behind it and the number of terms it added.  One thread per cell, a sum that runs away
+    from the mode: one result, bit for bit.  The caller owns every buffer and nothing is made here.  Returns (log_p, tail, steps)."""
+    _dev(count, size, csize, logfact, log_p, tail, steps)
+    assert count.dtype == torch.int32 and count.dim() == 2
+    k, N = count.shape[1], int(N)
+    assert 1 <= k <= ENRICH_MAX_K, f"k={k} outside 1 .. {ENRICH_MAX_K}"
+    assert 0 <= N <= ENRICH_MAX_N, f"N={N} outside 0 .. 2^24"
+    T, ldc = _rows(count, k, "count")
+    _vec(size, T, torch.int32, "size")
+    _vec(csize, k, torch.int32, "csize")
+    _vec(logfact, N + 1, torch.float64, "logfact")
+    assert log_p.dtype == torch.float64 and tail.dtype == torch.float64 and steps.dtype == torch.int32
+    assert tuple(log_p.shape) == tuple(tail.shape) == tuple(steps.shape) == (T, k)
+    ldo = _rows(log_p, k, "log_p")[1]
+    assert T <= 1 or (_rows(tail, k, "tail")[1] == ldo and _rows(steps, k, "steps")[1] == ldo), "log_p, tail and steps share one row stride"
+
+    def launch():
+        if T == 0:
+            return
+        check(_lib.load().vf_hypergeom_tail(count.data_ptr(), ldc, size.data_ptr(), csize.data_ptr(), T, k, N, logfact.data_ptr(),
+                                            int(alternative), log_p.data_ptr(), tail.data_ptr(), steps.data_ptr(), ldo, _stream()),
+              "vf_hypergeom_tail")
+    # operations: a few hundred fp64 + * / per cell is typical, the count depends on the cell; bytes: the three outputs and the counts
+    _run(launch, lambda: ("hypergeom_tail", 300.0 * T * k, 24.0 * T * k + 4.0 * (T + k) + 8.0 * (N + 1), f"T={T} k={k} N={N} alternative={int(alternative)}",
+                          family or _SCOPE))
+    return log_p, tail, steps
+
+
 def umap_smooth_knn_query(idx: torch.Tensor, dist: torch.Tensor, mean_dist: float, *, sigma: torch.Tensor, strength: torch.Tensor,
                           family: str = ""):
     """sigma and the directed membership strengths of every QUERY's list of training neighbours (vf_umap_smooth_knn_query,

@@ -369,6 +369,72 @@ class VCFProcessor:
         self._umap_columns(df, coords, labels, axis, prefix="tsne")
         return {"coords": coords, "labels": labels}
 
+    def expression_enrichment(self, df, annotations, labels=None, n_clusters=None, on: str = "predicted_expression", axis: str = "genes",
+                              tissue=None, **enrich_kwargs):
+        """Which annotation terms are over-represented in which cluster of genes: the "pathway enrichment"
+        the reference's vcf2embed notebook lists as a next step, over its gene -> GO term lists.  `df` is what format_output
+        returned; its genes are the universe.  `annotations` is a dict or a two-column frame, gene id -> list of terms.  `labels`
+        says how the genes are clustered:
+          a column name of `df`   its values, numbered in sorted order (a column of integers is taken as it is, negative = none);
+          an array                one integer per gene, 0 .. k - 1, any other value = in no cluster;
+          "max_tissue"            every gene's tissue of highest predicted expression (the notebook's Step 6);
+          None                    the Ward tree of the matrix neighbors.from_predictions(df, on, axis, tissue), cut into
+                                  `n_clusters` (linkage.ward_of_rows on the device, linkage.cut on the host).
+        The overlap counts and the hypergeometric tests run on the device (enrichment.enrich, which takes `enrich_kwargs`:
+        fdr=0.05, alternative="greater", min_size=5, max_size=500).  No model and no checkpoint are involved.  Adds the column
+        `enrichment_cluster` to `df` (the cluster's name: a number, a value of the column, a tissue) and returns enrich's dict,
+        with `cluster_names` and the tidy `frame` of significant (cluster, term) rows."""
+        from .. import enrichment, linkage, neighbors
+        if axis != "genes":
+            raise ValueError("enrichment tests clusters of genes: axis must be 'genes'")
+        for key in ("universe", "cluster_names", "n_clusters"):
+            if key in enrich_kwargs:
+                raise ValueError(f"expression_enrichment sets {key} itself")
+        if "gene_id" not in df.columns or len(df) == 0:
+            raise ValueError("the frame has no `gene_id` column or no rows: pass what format_output returned")
+        genes = list(df["gene_id"])
+        names = None
+        if labels is None:
+            if n_clusters is None:
+                raise ValueError("labels=None cuts the Ward tree of the genes: say into how many with n_clusters")
+            m, rows = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
+            if len(rows) != len(genes):
+                raise ValueError("embeddings of every tissue have (gene, tissue) rows: choose one `tissue` to cluster genes")
+            if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or not 1 <= n_clusters <= min(len(genes), enrichment.MAX_K):
+                raise ValueError(f"n_clusters must be an integer in 1 .. {min(len(genes), enrichment.MAX_K)}, not {n_clusters!r}")
+            lab = linkage.cut(linkage.ward_of_rows(m), int(n_clusters))
+            k = int(n_clusters)
+        elif isinstance(labels, str) and labels == "max_tissue":
+            m, _ = neighbors.from_predictions(df, on="predicted_expression", axis="genes")
+            lab = np.argmax(m, axis=1).astype(np.int32)
+            names = list(neighbors._tissue_names(df))
+            k = len(names)
+        elif isinstance(labels, str):
+            if labels not in df.columns:
+                raise ValueError(f"labels={labels!r} is neither a column of the frame nor 'max_tissue'")
+            values = df[labels].to_numpy()
+            if values.dtype != np.bool_ and np.issubdtype(values.dtype, np.integer):
+                lab, k = values.astype(np.int64), n_clusters
+            else:
+                missing = pd.isna(values)
+                names = sorted(set(values[~missing].tolist()))
+                lut = {v: i for i, v in enumerate(names)}
+                lab = np.array([-1 if miss else lut[v] for v, miss in zip(values.tolist(), missing)], dtype=np.int32)
+                k = len(names)
+        else:
+            lab, k = (np.asarray(labels) if isinstance(labels, (list, tuple)) else labels), n_clusters
+        out =enrichment.enrich(lab, annotations, genes, n_clusters=k, cluster_names=names, **enrich_kwargs)
+        k = out["cluster_size"].shape[0]
+        lab = np.asarray(lab.cpu() if isinstance(lab, torch.Tensor) else lab)
+        inside = (lab >= 0) & (lab < k)
+        shown = np.arange(k) if names is None else np.array(list(names), dtype=object)
+        column = np.where(inside, shown[np.where(inside, lab, 0)], -1 if names is None else None)
+        df["enrichment_cluster"] = pd.Series(column if names is not None else column.astype(np.int64), index=df.index,
+                                             dtype=object if names is not None else np.int64)
+        out["cluster_names"] = list(shown)
+        out["labels"] = lab.astype(np.int32)
+        return out
+
     @staticmethod
     def _umap_columns(df, coords, labels, axis, prefix: str = "umap"):
         if axis != "tissues":
