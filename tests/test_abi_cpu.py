@@ -30,6 +30,131 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert _lib.load().vf_version() == _lib.ABI_VERSION
 
 
+# ---------------------------------------------------------------------------------------------
+# the binding, type by type: every prototype of every header against the ctypes tables of _lib.py
+# ---------------------------------------------------------------------------------------------
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+_PROTOTYPE = re.compile(r"((?:const\s+)?\b(?:void|char|int|int32_t|int64_t|float|double)\b[\s\*]*?)\s*\b(vf_[a-z0-9_]+)\s*\(([^;{}()]*)\)\s*;")
+
+
+def _header_texts() -> dict:
+    inc = os.path.join(REPO, "include")
+    out = {}
+    for name in sorted(os.listdir(inc)):
+        if name.endswith(".h"):
+            with open(os.path.join(inc, name)) as f:
+                out[name] = f.read()
+    return out
+
+
+def _ctype_of(decl: str, what: str):
+    """The ctypes that may bind the C type of `decl` (a parameter with its name, or a return type): a tuple of the accepted ones."""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl:
+        words = [w for w in decl.split() if w not in ("const", "*")]
+        return (ctypes.c_void_p, ctypes.c_char_p) if words[0] == "char" else (ctypes.c_void_p,)
+    words = [w for w in decl.split() if w != "const"]
+    if words == ["void"]:
+        return (None,)
+    assert words[0] in _SCALARS, f"{what}: a C type this test does not map: {decl!r}"
+    return (_SCALARS[words[0]],)
+
+
+def _prototypes(text: str) -> dict:
+    """name -> (accepted restypes, [accepted argtypes per parameter]) of every vf_* prototype of a header's text; comments and
+    preprocessor lines are stripped first."""
+    src = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    src = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", " ", src, flags=re.M)
+    out = {}
+    for m in _PROTOTYPE.finditer(src):
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        assert name not in out, f"{name} is declared twice"
+        plist = [] if params in ("", "void") else [p.strip() for p in params.split(",")]
+        out[name] = (_ctype_of(ret, name), [_ctype_of(p, f"{name}({p})") for p in plist])
+    return out
+
+
+def _bound() -> dict:
+    """name -> (restype, argtypes) of every entry of every *_SIGNATURES dict of _lib.py, read off the loaded library."""
+    from variantformer_amd import _lib
+    lib = _lib.load()
+    out = {}
+    for table in sorted(n for n in vars(_lib) if n.endswith("SIGNATURES") and isinstance(getattr(_lib, n), dict)):
+        for name, argtypes in getattr(_lib, table).items():
+            assert name not in out, f"{name} is bound by two tables"
+            fn = getattr(lib, name)
+            assert fn.argtypes is not None, f"_lib.load() does not bind {name} of _lib.{table}"
+            assert list(fn.argtypes) == list(argtypes), f"{name}: load() bound other argtypes than _lib.{table} lists"
+            out[name] = (fn.restype, list(fn.argtypes))
+    return out
+
+
+def _binding_mismatches(declared: dict, bound: dict) -> list:
+    """One line per disagreement between the headers' prototypes and the binding, each naming its entry."""
+    bad = [f"{n}: declared in a header, bound by no table" for n in sorted(set(declared) - set(bound))]
+    bad += [f"{n}: bound, declared in no header" for n in sorted(set(bound) - set(declared))]
+    for name in sorted(set(declared) & set(bound)):
+        (ret_ok, params), (restype, argtypes) = declared[name], bound[name]
+        if restype not in ret_ok:
+            bad.append(f"{name}: restype {restype} where the header returns {[getattr(t, '__name__', t) for t in ret_ok]}")
+        if len(params) != len(argtypes):
+            bad.append(f"{name}: {len(argtypes)} argtypes for {len(params)} declared parameters")
+            continue
+        for i, (ok, got) in enumerate(zip(params, argtypes)):
+            if got not in ok:
+                bad.append(f"{name}: parameter {i} is bound as {got.__name__}, the header wants {[t.__name__ for t in ok]}")
+    return bad
+
+
+def _all_declared(texts: dict) -> dict:
+    declared = {}
+    for header, text in texts.items():
+        for name, proto in _prototypes(text).items():
+            assert name not in declared, f"{name} is declared in two headers"
+            declared[name] = proto
+    return declared
+
+
+def test_every_binding_matches_its_prototype_type_by_type():
+    """Parameter by parameter and the return type: a c_int for an int64_t, a c_float for a double or a missing argument would load
+    and run with garbage in a register.  Every header under include/, every *_SIGNATURES table of _lib.py."""
+    from variantformer_amd import _lib
+    texts = _header_texts()
+    assert len(texts) >= 14 and "vf_hip.h" in texts
+    declared, bound = _all_declared(texts), _bound()
+    assert sorted(_prototypes(texts["vf_hip.h"])) == _declared()            # the parser sees what the name test sees
+    assert len(declared) >= 82
+    assert _binding_mismatches(declared, bound) == []
+    # load() binds every table the module defines: a table it forgot leaves ctypes' default int arguments in place
+    tables = [n for n in vars(_lib) if n.endswith("SIGNATURES")]
+    assert len(tables) >= 14 and sum(len(getattr(_lib, n)) for n in tables) == len(bound) == len(declared)
+    assert set(_lib._RESTYPES) <= set(bound)
+
+
+def test_the_type_comparison_names_a_mutated_entry():
+    """On a copy of a header's text: an int64_t stride as int, a dropped parameter, a float as double -- each is reported, under
+    the entry's name, and nothing else is."""
+    texts = _header_texts()
+    bound = _bound()
+    text = texts["vf_hip_linkage.h"]
+    mutations = {
+        "vf_linkage_nearest": ("int vf_linkage_nearest(const float* D, int64_t ld,", "int vf_linkage_nearest(const float* D, int ld,",
+                               "parameter 1 is bound as c_long"),
+        "vf_linkage_contract": ("float* pair_dist, int upper_only,", "float* pair_dist,", "13 argtypes for 12 declared parameters"),
+    }
+    for entry, (old, new, message) in mutations.items():
+        assert text.count(old) == 1
+        bad = _binding_mismatches(_all_declared({**texts, "vf_hip_linkage.h": text.replace(old, new)}), bound)
+        assert len(bad) == 1 and bad[0].startswith(entry + ":") and message in bad[0].replace("c_int64", "c_long"), bad
+    text = texts["vf_hip_umap.h"]
+    proto = re.search(r"int vf_umap_smooth_knn\([^;]*;", text).group(0)
+    assert proto.count("float ") == 1                                           # its one scalar float: mean_dist
+    bad = _binding_mismatches(_all_declared({**texts, "vf_hip_umap.h": text.replace(proto, proto.replace("float ", "double "))}), bound)
+    assert len(bad) == 1 and bad[0].startswith("vf_umap_smooth_knn: parameter 6 is bound as c_float"), bad
+
+
 def test_argument_validation_without_gpu():
     """Error behaviour of the boundary: invalid arguments are rejected before any launch."""
     from variantformer_amd import _lib

@@ -51,6 +51,10 @@ GUARD_ROWS, GUARD_COLS = 256, 8
 DEVICE = "cuda"
 TDT = {"bf16": torch.bfloat16, "fp16": torch.float16}
 WRAPPER_MODULES = ("variantformer_amd.ops", "variantformer_amd.attn_maps", "variantformer_amd.seq2gene.modules.layers")
+# the analysis pipelines: their out= buffers and workspaces are allocated by the pipeline, not by the wrappers of ops.py
+# (tests/analysis_pipeline_cases.py); poisoned only where a caller passes modules=
+ANALYSIS_MODULES = ("variantformer_amd.manifold", "variantformer_amd.linkage", "variantformer_amd.enrichment",
+                    "variantformer_amd.neighbors", "variantformer_amd.processors.ad_risk")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -94,20 +98,20 @@ class TorchProxy:
         return self._hand_out(torch.empty_like(*args, **kw))
 
 
-def install(monkeypatch, pattern: int, keep: bool = True) -> TorchProxy:
-    """Replace the `torch` name of the wrapper modules with a poisoning proxy; monkeypatch undoes it."""
+def install(monkeypatch, pattern: int, keep: bool = True, modules=None) -> TorchProxy:
+    """Replace the `torch` name of the wrapper modules (or of `modules`) with a poisoning proxy; monkeypatch undoes it."""
     import importlib
     proxy = TorchProxy(pattern, keep)
-    for name in WRAPPER_MODULES:
+    for name in WRAPPER_MODULES if modules is None else modules:
         monkeypatch.setattr(importlib.import_module(name), "torch", proxy)
     return proxy
 
 
 @contextlib.contextmanager
-def poison_allocations(pattern: int, keep: bool = True):
+def poison_allocations(pattern: int, keep: bool = True, modules=None):
     import pytest
     with pytest.MonkeyPatch.context() as mp:
-        yield install(mp, pattern, keep)
+        yield install(mp, pattern, keep, modules)
 
 
 def guarded(x: torch.Tensor, pattern: int, cols: int = 0, device=None, rows: int = GUARD_ROWS) -> torch.Tensor:
