@@ -1,7 +1,7 @@
 """ctypes binding of libvf_hip.so (C ABI declared in include/vf_hip.h, include/vf_hip_next.h, include/vf_hip_gene_contrib.h,
 include/vf_hip_cre_heads.h, include/vf_hip_forest.h, include/vf_hip_topk.h, include/vf_hip_neighbors.h, include/vf_hip_linkage.h,
 include/vf_hip_umap.h, include/vf_hip_spectral.h, include/vf_hip_umap_transform.h, include/vf_hip_components.h,
-include/vf_hip_tsne.h and include/vf_hip_enrich.h).
+include/vf_hip_tsne.h, include/vf_hip_enrich.h and include/vf_kmeans.h).
 
 The product path has NO fallback: if the shared library is missing, cannot be loaded, or lacks a
 declared symbol, importing the ops raises.  Signatures are plain pointers and sizes; torch only
@@ -20,7 +20,7 @@ VF_F32, VF_BF16, VF_F16 = 0, 1, 2
 EPI_BF16, EPI_F32, EPI_RES_F32, EPI_GEGLU_BF16, EPI_GELU_F32, EPI_GELU_BF16 = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 13
 
-_p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> argtypes (restype is int unless noted); mirrors include/vf_hip.h one to one
 SIGNATURES = {
@@ -146,6 +146,13 @@ ENRICH_SIGNATURES = {
     "vf_enrich_counts": [_p, _p, _l, _l, _p, _l, _i, _p, _l, _p, _p],
     "vf_hypergeom_tail": [_p, _l, _p, _p, _l, _i, _l, _p, _i, _p, _p, _p, _l, _p],
 }
+# the entries declared in include/vf_kmeans.h (k-means: the nearest centre, the fp64 means, Lloyd's loop, D^2 seeding); bound exactly like SIGNATURES
+KMEANS_SIGNATURES = {
+    "vf_kmeans_assign": [_p, _l, _l, _i, _p, _l, _i, _p, _p, _p],
+    "vf_kmeans_update": [_p, _l, _l, _i, _p, _p, _l, _i, _p, _l, _p, _p],
+    "vf_kmeans_lloyd": [_p, _l, _l, _i, _p, _l, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p],
+    "vf_kmeans_seed": [_p, _l, _l, _i, _i, _l, _p, _p, _l, _p, _p, _l, _p],
+}
 _RESTYPES = {"vf_last_error": C.c_char_p, "vf_last_kernel": C.c_char_p, "vf_bpe_create": C.c_void_p, "vf_bpe_destroy": None, "vf_bpe_encode": C.c_int64, "vf_bpe_encode_prefix": C.c_int64,
              "vf_vcf_open": C.c_void_p, "vf_vcf_close": None, "vf_vcf_num_records": C.c_int64,
              "vf_vcf_consensus": C.c_int64, "vf_build_windows": C.c_int64}
@@ -177,7 +184,7 @@ def load(path: str | None = None):
                            list(CRE_HEADS_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + list(TOPK_SIGNATURES.items()) +
                            list(NEIGHBORS_SIGNATURES.items()) + list(LINKAGE_SIGNATURES.items()) + list(UMAP_SIGNATURES.items()) +
                            list(SPECTRAL_SIGNATURES.items()) + list(UMAP_TRANSFORM_SIGNATURES.items()) + list(COMPONENTS_SIGNATURES.items()) +
-                           list(TSNE_SIGNATURES.items()) + list(ENRICH_SIGNATURES.items())):
+                           list(TSNE_SIGNATURES.items()) + list(ENRICH_SIGNATURES.items()) + list(KMEANS_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

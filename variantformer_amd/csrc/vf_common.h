@@ -17,6 +17,7 @@
 #include "../../include/vf_hip_components.h"
 #include "../../include/vf_hip_tsne.h"
 #include "../../include/vf_hip_enrich.h"
+#include "../../include/vf_kmeans.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;

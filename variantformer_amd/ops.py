@@ -1232,6 +1232,134 @@ def hypergeom_tail(count: torch.Tensor, size: torch.Tensor, csize: torch.Tensor,
     return log_p, tail, steps
 
 
+# include/vf_kmeans.h: VF_KMEANS_MAX_K, _MAX_R, _MAX_D, _ROWS, _UPDATE_COLS, _RED_THREADS
+KMEANS_MAX_K, KMEANS_MAX_R, KMEANS_MAX_D, KMEANS_ROWS, KMEANS_UPDATE_COLS, KMEANS_RED_THREADS = 4096, 1 << 24, 65536, 64, 64, 256
+
+
+def kmeans_lloyd_work_bytes(R: int, d: int, k: int) -> int:
+    """VF_KMEANS_LLOYD_WORK_BYTES(R, d, k)."""
+    return 8 + 8 * k * ((d + KMEANS_UPDATE_COLS - 1) // KMEANS_UPDATE_COLS) + 4 * ((R + KMEANS_ROWS - 1) // KMEANS_ROWS)
+
+
+def kmeans_seed_work_bytes(R: int) -> int:
+    """VF_KMEANS_SEED_WORK_BYTES(R)."""
+    return 16 + 12 * ((R + KMEANS_RED_THREADS - 1) // KMEANS_RED_THREADS)
+
+
+def _kmeans_operands(x: torch.Tensor, cen: torch.Tensor, name: str = "cen"):
+    assert x.dtype == torch.float32 and cen.dtype == torch.float32 and x.dim() == 2 and cen.dim() == 2 and x.shape[1] == cen.shape[1]
+    d = x.shape[1]
+    assert 1 <= d <= KMEANS_MAX_D, f"d={d} outside 1 .. {KMEANS_MAX_D}"
+    R, ldx = _rows(x, d, "x")
+    k, ldc = _rows(cen, d, name)
+    assert 1 <= k <= KMEANS_MAX_K, f"k={k} outside 1 .. {KMEANS_MAX_K}"
+    assert R <= KMEANS_MAX_R, f"R={R} is above 2^24"
+    return R, d, ldx, k, ldc
+
+
+def kmeans_assign(x: torch.Tensor, cen: torch.Tensor, *, labels: torch.Tensor, dist: torch.Tensor, family: str = ""):
+    """The nearest centre of every row (vf_kmeans_assign, include/vf_kmeans.h).  x fp32 [R, d] and cen fp32 [k, d] row-strided,
+    only read; labels int32 [R] and dist fp32 [R] contiguous.  The squared distance is a running fp32 sum of (x - c)^2 over the
+    columns in ascending order, every operation rounded once, no fma; the smallest wins, ties to the lower centre, a NaN never;
+    a row with no winner has label -1 and dist NaN.  The caller owns every buffer and nothing is made here.  Returns
+    (labels, dist)."""
+    _dev(x, cen, labels, dist)
+    R, d, ldx, k, ldc = _kmeans_operands(x, cen)
+    _vec(labels, R, torch.int32, "labels")
+    _vec(dist, R, torch.float32, "dist")
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_kmeans_assign(x.data_ptr(), ldx, R, d, cen.data_ptr(), ldc, k, labels.data_ptr(), dist.data_ptr(), _stream()),
+              "vf_kmeans_assign")
+    _run(launch, lambda: ("kmeans_assign", 3.0 * R * k * d, 4.0 * (R * d + k * d + 2 * R), f"R={R} d={d} k={k}", family or _SCOPE))
+    return labels, dist
+
+
+def kmeans_update(x: torch.Tensor, labels: torch.Tensor, cen_old: torch.Tensor, *, cen_new: torch.Tensor, counts: torch.Tensor,
+                  family: str = ""):
+    """The fp64 mean of every cluster's rows (vf_kmeans_update, include/vf_kmeans.h).  x fp32 [R, d] row-strided and labels int32
+    [R], only read (a label outside 0 .. k - 1 belongs to no centre); cen_old fp32 [k, d] row-strided; cen_new fp32 [k, d]
+    row-strided, which may be cen_old itself; counts int32 [k].  The sums run over VF_KMEANS_UPDATE_WAVES contiguous row ranges
+    in ascending row order and are added in range order; a centre without members keeps cen_old's bits.  No atomic: one result,
+    bit for bit.  The caller owns every buffer and nothing is made here.  Returns (cen_new, counts)."""
+    _dev(x, labels, cen_old, cen_new, counts)
+    R, d, ldx, k, ldc = _kmeans_operands(x, cen_old, "cen_old")
+    assert cen_new.dtype == torch.float32 and cen_new.dim() == 2 and tuple(cen_new.shape) == (k, d)
+    ldn = _rows(cen_new, d, "cen_new")[1]
+    _vec(labels, R, torch.int32, "labels")
+    _vec(counts, k, torch.int32, "counts")
+
+    def launch():
+        # R == 0: nothing reads x or labels, and an empty tensor has no address: `cen_old` stands in for them
+        check(_lib.load().vf_kmeans_update(x.data_ptr() if R else cen_old.data_ptr(), ldx, R, d, labels.data_ptr() if R else cen_old.data_ptr(),
+                                           cen_old.data_ptr(), ldc, k, cen_new.data_ptr(), ldn, counts.data_ptr(), _stream()), "vf_kmeans_update")
+    _run(launch, lambda: ("kmeans_update", 1.0 * R * d, 4.0 * (R * d + R * k * ((d + 63) // 64) + 2 * k * d + k), f"R={R} d={d} k={k}",
+                          family or _SCOPE))
+    return cen_new, counts
+
+
+def kmeans_lloyd(x: torch.Tensor, cen: torch.Tensor, *, max_iter: int, tol_abs: float, resume: bool = False, labels: torch.Tensor,
+                 dist: torch.Tensor, prev_labels: torch.Tensor, counts: torch.Tensor, n_iter: torch.Tensor, shift: torch.Tensor,
+                 changed: torch.Tensor, work: torch.Tensor, family: str = ""):
+    """Up to max_iter iterations of Lloyd's loop and a last assignment (vf_kmeans_lloyd, include/vf_kmeans.h), from one loop inside
+    the library with the stop decided on the device: scikit-learn's _kmeans_single_lloyd.  x fp32 [R, d] row-strided, only read;
+    cen fp32 [k, d] row-strided: in, the start; out, the result.  labels int32 [R] and dist fp32 [R]: the last assignment;
+    prev_labels int32 [R]: the labels of the last iteration that ran (read with resume=True); counts int32 [k]; n_iter int32 [1];
+    shift fp64 [max_iter] and changed int64 [max_iter], written up to n_iter alone; work a contiguous buffer of at least
+    kmeans_lloyd_work_bytes(R, d, k) bytes.  An iteration stops the loop when no label changed (not the first of a fresh run) or
+    when the summed squared shift of the centres is <= tol_abs.  One result, bit for bit; a then b iterations on the carried
+    state equal a + b.  The caller owns every buffer and nothing is made here.  Returns (cen, labels, dist, n_iter)."""
+    _dev(x, cen, labels, dist, prev_labels, counts, n_iter, shift, changed, work)
+    R, d, ldx, k, ldc = _kmeans_operands(x, cen)
+    max_iter = int(max_iter)
+    assert max_iter >= 0, f"max_iter={max_iter} must not be negative"
+    _vec(labels, R, torch.int32, "labels")
+    _vec(dist, R, torch.float32, "dist")
+    _vec(prev_labels, R, torch.int32, "prev_labels")
+    _vec(counts, k, torch.int32, "counts")
+    _vec(n_iter, 1, torch.int32, "n_iter")
+    _vec(shift, max_iter, torch.float64, "shift")
+    _vec(changed, max_iter, torch.int64, "changed")
+    assert work.is_contiguous(), "work: a contiguous buffer"
+    work_bytes = work.numel() * work.element_size()
+
+    def launch():
+        if R == 0:
+            return
+        check(_lib.load().vf_kmeans_lloyd(x.data_ptr(), ldx, R, d, cen.data_ptr(), ldc, k, max_iter, float(tol_abs), int(bool(resume)),
+                                          labels.data_ptr(), dist.data_ptr(), prev_labels.data_ptr(), counts.data_ptr(), n_iter.data_ptr(),
+                                          shift.data_ptr() if max_iter else 0, changed.data_ptr() if max_iter else 0, work.data_ptr(),
+                                          work_bytes, _stream()), "vf_kmeans_lloyd")
+    _run(launch, lambda: ("kmeans_lloyd", 3.0 * R * k * d * (max_iter + 1), 4.0 * (max_iter + 1) * (R * d + k * d + 2 * R),
+                          f"R={R} d={d} k={k} max_iter={max_iter}", family or _SCOPE))
+    return cen, labels, dist, n_iter
+
+
+def kmeans_seed(x: torch.Tensor, k: int, seed: int, *, rows: torch.Tensor, cen: torch.Tensor, mind: torch.Tensor, work: torch.Tensor,
+                family: str = ""):
+    """Plain D^2 seeding (vf_kmeans_seed, include/vf_kmeans.h): k rows of x, each drawn with probability proportional to its
+    squared distance to the nearest row drawn before, in exact integer arithmetic from a counter hash of (seed, step).  x fp32
+    [R, d] row-strided, only read; rows int32 [k]: the chosen rows; cen fp32 [k, d] row-strided: copies of them; mind fp32 [R];
+    work a contiguous buffer of at least kmeans_seed_work_bytes(R) bytes.  One result, bit for bit, which numpy restates
+    (tests/kmeans_cases.py).  The caller owns every buffer and nothing is made here.  Returns (rows, cen)."""
+    _dev(x, rows, cen, mind, work)
+    R, d, ldx, kc, ldc = _kmeans_operands(x, cen)
+    k = int(k)
+    assert kc == k and 1 <= k <= R, f"k={k}: cen has {kc} rows, x has {R}"
+    _vec(rows, k, torch.int32, "rows")
+    _vec(mind, R, torch.float32, "mind")
+    assert work.is_contiguous(), "work: a contiguous buffer"
+    work_bytes = work.numel() * work.element_size()
+
+    def launch():
+        check(_lib.load().vf_kmeans_seed(x.data_ptr(), ldx, R, d, k, int(seed), rows.data_ptr(), cen.data_ptr(), ldc, mind.data_ptr(),
+                                         work.data_ptr(), work_bytes, _stream()), "vf_kmeans_seed")
+    _run(launch, lambda: ("kmeans_seed", 3.0 * R * d * k, 4.0 * k * (R * d + 3 * R), f"R={R} d={d} k={k}", family or _SCOPE))
+    return rows, cen
+
+
 def umap_smooth_knn_query(idx: torch.Tensor, dist: torch.Tensor, mean_dist: float, *, sigma: torch.Tensor, strength: torch.Tensor,
                           family: str = ""):
     """sigma and the directed membership strengths of every QUERY's list of training neighbours (vf_umap_smooth_knn_query,

@@ -436,6 +436,66 @@ class VCFProcessor:
         return out
 
     @staticmethod
+    def _kmeans_matrix(df, on, axis, tissue):
+        """(matrix, labels, metric forced or None) of expression_kmeans: a from_predictions matrix, or the frame's own umap_1 ..
+        / tsne_1 .. columns."""
+        import re
+        from .. import neighbors
+        if on in ("umap", "tsne"):
+            if axis != "genes" or tissue is not None:
+                raise ValueError(f"on={on!r} clusters the frame's {on}_1 .. columns: one row per gene, no tissue")
+            cols = sorted((c for c in df.columns if isinstance(c, str) and re.fullmatch(rf"{on}_[1-9]\d*", c)), key=lambda c: int(c.split("_")[1]))
+            if not cols or "gene_id" not in df.columns or len(df) == 0:
+                raise ValueError(f"the frame has no {on}_1 .. columns (run expression_{on} first), no `gene_id` column or no rows")
+            try:
+                m = np.ascontiguousarray(df[cols].to_numpy(dtype=np.float32))
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"the {on}_1 .. columns hold one array per gene ((gene, tissue) rows): they cannot be clustered as genes") from e
+            return m, list(df["gene_id"]), "euclidean"
+        m, labels = neighbors.from_predictions(df, on=on, axis=axis, tissue=tissue)
+        return m, labels, None
+
+    def expression_kmeans(self, df, n_clusters, on: str = "predicted_expression", axis: str = "genes", tissue=None, **kmeans_kwargs):
+        """Flat clusters of a finished prediction: the k-means the vcf2embed notebook's "GO term enrichment
+        within UMAP clusters" needs.  `df` is what format_output returned.  on="predicted_expression" / "embeddings" cluster the
+        matrix neighbors.from_predictions(df, on, axis, tissue); on="umap" / "tsne" cluster the frame's umap_1 .. / tsne_1 ..
+        columns with metric="euclidean".  Lloyd's loop and the seeding run on the device (kmeans.kmeans, which takes
+        `kmeans_kwargs`: metric="correlation", init="k-means++", n_init=1, max_iter=300, tol=1e-4, seed=0).  No model and no
+        checkpoint are involved.  Returns a dict: labels int32 [rows], centers fp32 [k, columns], inertia, n_iter, and `model`, the
+        kmeans.KMeansModel that expression_kmeans_assign takes.  Where the rows are genes the integer column `kmeans_cluster` is
+        added to `df`: expression_enrichment(df, annotations, labels="kmeans_cluster", n_clusters=k) takes it as it is."""
+        from .. import kmeans
+        m, labels, metric = self._kmeans_matrix(df, on, axis, tissue)
+        if metric is not None:
+            if kmeans_kwargs.get("metric", metric) != metric:
+                raise ValueError(f"on={on!r} clusters coordinates: metric must be {metric!r}")
+            kmeans_kwargs["metric"] = metric
+        model = kmeans.kmeans(m, n_clusters, **kmeans_kwargs)
+        if axis == "genes" and len(labels) == len(df):
+            df["kmeans_cluster"] = pd.Series(np.asarray(model.labels, dtype=np.int64), index=df.index, dtype=np.int64)
+        return {"labels": model.labels, "centers": model.centers, "inertia": model.inertia, "n_iter": model.n_iter, "model": model,
+                "row_labels": labels}
+
+    def expression_kmeans_assign(self, model, df, on: str = "predicted_expression", axis: str = "genes", tissue=None):
+        """The clusters of a first prediction for the rows of a second: `model` is what expression_kmeans
+        returned under "model", `df` what format_output returned for another individual (with its umap_1 .. columns from
+        expression_umap_transform for on="umap").  Every row gets its nearest fitted centre (model.predict: an assignment alone).
+        Returns {"labels": int32 [rows], "distance": fp32 [rows], "row_labels"} and adds the column `kmeans_cluster` to `df`
+        under expression_kmeans's rule."""
+        from .. import kmeans
+        if not isinstance(model, kmeans.KMeansModel):
+            raise TypeError(f"model must be a kmeans.KMeansModel (expression_kmeans(...)['model']), not {type(model).__name__}")
+        m, labels, metric = self._kmeans_matrix(df, on, axis, tissue)
+        if metric is not None and model.metric != metric:
+            raise ValueError(f"on={on!r} assigns coordinates: the model was fitted with metric={model.metric!r}")
+        if m.shape[1] != model.columns:
+            raise ValueError(f"the frame's matrix has {m.shape[1]} columns, the model was fitted on {model.columns}")
+        lab, dist = model.predict(m, return_distance=True)
+        if axis == "genes" and len(labels) == len(df):
+            df["kmeans_cluster"] = pd.Series(np.asarray(lab, dtype=np.int64), index=df.index, dtype=np.int64)
+        return {"labels": lab, "distance": dist, "row_labels": labels}
+
+    @staticmethod
     def _umap_columns(df, coords, labels, axis, prefix: str = "umap"):
         if axis != "tissues":
             per = len(labels) // len(df)                                 # 1, or the tissues of a (gene, tissue) row set
