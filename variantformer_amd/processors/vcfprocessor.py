@@ -495,6 +495,55 @@ class VCFProcessor:
             df["kmeans_cluster"] = pd.Series(np.asarray(lab, dtype=np.int64), index=df.index, dtype=np.int64)
         return {"labels": lab, "distance": dist, "row_labels": labels}
 
+    def expression_silhouette(self, df, labels="kmeans_cluster", on: str = "predicted_expression", axis: str = "genes", tissue=None,
+                              metric=None, standardize=None, max_bytes=None):
+        """How well a flat clustering of a finished prediction separates: the silhouette coefficient,
+        scikit-learn's silhouette_samples, on the device (validation.silhouette_samples).  `df` is what format_output returned;
+        the matrix is expression_kmeans's: neighbors.from_predictions(df, on, axis, tissue), or the frame's umap_1 .. / tsne_1 ..
+        columns for on="umap" / "tsne".  `labels` names a column of `df` (the default is expression_kmeans's `kmeans_cluster`;
+        `enrichment_cluster` and any column of one's own serve too) or is an array with one label per row of the matrix; a
+        negative label is no label.  metric: "correlation" (the default for a matrix; linear in the rows), "cosine" or
+        "euclidean" (the default, and the only one, for coordinates); standardize as in validation.silhouette_samples.  Where the
+        rows are genes the columns `silhouette` (NaN for a gene without a label) and `silhouette_neighbor_cluster` (the label of
+        the nearest other cluster: where the gene would go next) are added to `df`.  Returns the score, the mean over the
+        labelled rows."""
+        from .. import validation
+        m, row_labels, forced = self._kmeans_matrix(df, on, axis, tissue)
+        if forced is not None and metric not in (None, forced):
+            raise ValueError(f"on={on!r} scores coordinates: metric must be {forced!r}")
+        metric = forced or metric or "correlation"
+        if isinstance(labels, str):
+            if labels not in df.columns:
+                raise ValueError(f"the frame has no `{labels}` column: run expression_kmeans first, or pass the labels themselves")
+            if len(row_labels) != len(df):
+                raise ValueError(f"the column `{labels}` has one label per gene, the matrix has {len(row_labels)} rows: pass an array")
+            labels = df[labels].to_numpy()
+        kwargs = {} if max_bytes is None else {"max_bytes": max_bytes}
+        res = validation.silhouette_samples(m, labels, metric=metric, standardize=standardize, **kwargs)
+        if axis == "genes" and len(row_labels) == len(df):
+            df["silhouette"] = pd.Series(np.asarray(res.samples, dtype=np.float64), index=df.index, dtype=np.float64)
+            df["silhouette_neighbor_cluster"] = pd.Series(res.nearest, index=df.index)
+        return res.score
+
+    def expression_silhouette_sweep(self, df, ks, method: str = "kmeans", on: str = "predicted_expression", axis: str = "genes", tissue=None,
+                                    metric=None, **kwargs):
+        """Which number of clusters?  Clusters the matrix of expression_silhouette at every k of `ks`
+        (validation.silhouette_sweep: method="kmeans", which takes kmeans.kmeans's `kwargs`, or method="ward", one tree cut once
+        per k) and scores each clustering by its silhouette.  Returns a small frame, one row per k: `k`, `silhouette_score` and,
+        for k-means, `inertia`; frame.attrs["best_k"] is the k of the largest score and frame.attrs["labels"] maps every k to its
+        int32 labels."""
+        from .. import validation
+        m, _, forced = self._kmeans_matrix(df, on, axis, tissue)
+        if forced is not None and metric not in (None, forced):
+            raise ValueError(f"on={on!r} scores coordinates: metric must be {forced!r}")
+        res = validation.silhouette_sweep(m, ks, method=method, metric=forced or metric or "correlation", **kwargs)
+        out = pd.DataFrame({"k": np.asarray(res.ks, dtype=np.int64), "silhouette_score": np.asarray(res.scores, dtype=np.float64)})
+        if res.inertia is not None:
+            out["inertia"] = np.asarray(res.inertia, dtype=np.float64)
+        out.attrs["best_k"] = res.best_k
+        out.attrs["labels"] = dict(zip(res.ks, res.labels))
+        return out
+
     @staticmethod
     def _umap_columns(df, coords, labels, axis, prefix: str = "umap"):
         if axis != "tissues":
