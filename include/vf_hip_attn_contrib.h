@@ -1,16 +1,16 @@
-/* vf_hip_next.h -- entries of libvf_hip.so that still wait for their case in the main write-set net.
+/* vf_hip_attn_contrib.h -- the entry of libvf_hip.so behind the cCRE contribution maps.
  *
- * tests/write_set_cases.py holds one poisoned-memory case for every stream-taking declaration of vf_hip.h, and the binding test
- * holds _lib.SIGNATURES to that header's names.  An entry added by a change that may not edit those files is declared here
- * instead, bound through _lib.NEXT_SIGNATURES (applied by _lib.load() exactly like SIGNATURES), and covered by a parallel net of
+ * tests/write_set_cases.py holds one poisoned-memory case for every stream-taking declaration of vf_hip.h.  This entry is
+ * declared here instead, bound through _lib.ENTRIES["vf_hip_attn_contrib.h"] (tests/test_abi_cpu.py holds every header to its
+ * table), and covered by a parallel net of
  * its own (tests/attn_contrib_cases.py, tests/test_attn_contrib_cpu.py: every stream-taking declaration of THIS header has a
- * write-set case there).  Moving a declaration into vf_hip.h, together with its case, is the follow-up.  Everything the main
+ * write-set case there).  Everything the main
  * header says holds here: the conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in
  * elements, 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write set, non-finite operands,
  * refusals), and VF_ABI_VERSION: a new symbol changes no existing one, so the version stays 13.
  */
-#ifndef VF_HIP_NEXT_H
-#define VF_HIP_NEXT_H
+#ifndef VF_HIP_ATTN_CONTRIB_H
+#define VF_HIP_ATTN_CONTRIB_H
 
 #include "vf_hip.h"
 
@@ -55,4 +55,4 @@ int vf_attn_contrib(const void* v, int64_t v_stride, const float* s_gram, const 
 #ifdef __cplusplus
 }
 #endif
-#endif /* VF_HIP_NEXT_H */
+#endif /* VF_HIP_ATTN_CONTRIB_H */

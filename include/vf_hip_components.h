@@ -4,9 +4,9 @@
  * of each component's rows of a matrix.  Three entries, driven by variantformer_amd/manifold.py (_components,
  * spectral_init_components), which sorts the labels with torch and solves every component with the entries of vf_hip_spectral.h.
  *
- * The twelfth header of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * The twelfth header of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
  * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h, vf_hip_linkage.h, vf_hip_umap.h, vf_hip_spectral.h and
- * vf_hip_umap_transform.h.  Its entries are bound through _lib.COMPONENTS_SIGNATURES, which _lib.load() applies like the other
+ * vf_hip_umap_transform.h.  Its entries are bound through _lib.ENTRIES["vf_hip_components.h"], which _lib.load() applies like the other
  * eleven tables, and tests/components_cases.py holds their references and case table.  Everything the main header says holds
  * here: the conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok /
  * VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write set, arithmetic, refusals), and

@@ -1,7 +1,7 @@
 /* vf_hip_cre_heads.h -- the entry of libvf_hip.so behind the tokenizer's per-tissue classifier heads (cCRE activity classes).
  *
- * One of six headers of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_forest.h and vf_hip_topk.h.  Its entry is bound
- * through _lib.CRE_HEADS_SIGNATURES, which _lib.load() applies like the other five tables, and every stream-taking declaration here has
+ * One of six headers of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_forest.h and vf_hip_topk.h.  Its entry is bound
+ * through _lib.ENTRIES["vf_hip_cre_heads.h"], which _lib.load() applies like the other five tables, and every stream-taking declaration here has
  * poisoned-memory write-set cases in tests/cre_heads_cases.py.  Everything the main header says holds here: the conventions at
  * its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok / VF_ERR_*,
  * vf_last_error()), the comment contract of every entry (arguments, write set, non-finite operands, refusals), and

@@ -6,9 +6,9 @@
  * (membership, hypergeom, enrich), which builds the CSR arrays and the table of log-factorials on the host and does the
  * Benjamini-Hochberg step with torch.
  *
- * The fourteenth header of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * The fourteenth header of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
  * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h, vf_hip_linkage.h, vf_hip_umap.h, vf_hip_spectral.h,
- * vf_hip_umap_transform.h, vf_hip_components.h and vf_hip_tsne.h.  Its entries are bound through _lib.ENRICH_SIGNATURES, which
+ * vf_hip_umap_transform.h, vf_hip_components.h and vf_hip_tsne.h.  Its entries are bound through _lib.ENTRIES["vf_hip_enrich.h"], which
  * _lib.load() applies like the other thirteen tables, and tests/enrich_cases.py holds their references and case table.
  * Everything the main header says holds here: the conventions at its top (device pointers owned by the caller, `stream` a
  * hipStream_t, strides in elements, 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write

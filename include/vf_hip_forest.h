@@ -1,7 +1,7 @@
 /* vf_hip_forest.h -- the entry of libvf_hip.so behind the per-(gene, tissue) forest predictors on embeddings (AD risk).
  *
- * One of six headers of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h and vf_hip_topk.h.  Its
- * entry is bound through _lib.FOREST_SIGNATURES, which _lib.load() applies like the other five tables, and every stream-taking
+ * One of six headers of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h and vf_hip_topk.h.  Its
+ * entry is bound through _lib.ENTRIES["vf_hip_forest.h"], which _lib.load() applies like the other five tables, and every stream-taking
  * declaration here has poisoned-memory write-set cases in tests/forest_cases.py.  Everything the main header says holds here:
  * the conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok /
  * VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write set, arithmetic, non-finite operands,

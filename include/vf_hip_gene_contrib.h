@@ -1,11 +1,11 @@
 /* vf_hip_gene_contrib.h -- the entry of libvf_hip.so behind the gene-body contribution maps.
  *
- * tests/write_set_cases.py holds one poisoned-memory case for every stream-taking declaration of vf_hip.h and the binding test
- * holds _lib.SIGNATURES to that header's names; tests/test_attn_contrib_cpu.py holds vf_hip_next.h to exactly its one name.  An
- * entry added by a change that may edit neither is declared here instead, bound through _lib.GENE_CONTRIB_SIGNATURES (applied by
- * _lib.load() exactly like SIGNATURES and NEXT_SIGNATURES), and covered by a parallel net of its own (tests/gene_contrib_cases.py,
- * tests/test_gene_contrib_cpu.py: every stream-taking declaration of THIS header has a write-set case there).  Folding the
- * three headers together, with their cases, is the follow-up.  Everything the main header says holds here: the conventions at
+ * tests/write_set_cases.py holds one poisoned-memory case for every stream-taking declaration of vf_hip.h;
+ * tests/test_attn_contrib_cpu.py holds vf_hip_attn_contrib.h to exactly its one name.  This entry is declared here instead, bound
+ * through _lib.ENTRIES["vf_hip_gene_contrib.h"] (tests/test_abi_cpu.py holds every header to its table), and covered by a parallel
+ * net of its own (tests/gene_contrib_cases.py,
+ * tests/test_gene_contrib_cpu.py: every stream-taking declaration of THIS header has a write-set case there).  Everything the
+ * main header says holds here: the conventions at
  * its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok / VF_ERR_*,
  * vf_last_error()), the comment contract of every entry (arguments, write set, non-finite operands, refusals), and
  * VF_ABI_VERSION: a new symbol changes no existing one, so the version stays 13.

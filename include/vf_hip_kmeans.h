@@ -1,11 +1,11 @@
-/* vf_kmeans.h -- the entries of libvf_hip.so behind k-means clustering (scikit-learn's KMeans(algorithm="lloyd")): the
+/* vf_hip_kmeans.h -- the entries of libvf_hip.so behind k-means clustering (scikit-learn's KMeans(algorithm="lloyd")): the
  * assignment of every row to its nearest centre, the fp64 means of the clusters, all iterations of Lloyd's loop with the stop
  * decided on the device, and plain D^2 seeding (Arthur-Vassilvitskii) with integer sampling.  Every sum has a stated order and
  * there is no atomic, so two runs are equal bit for bit, a run can be split at any iteration, and numpy restates every entry bit
  * for bit (tests/kmeans_cases.py).  The stages are driven by variantformer_amd/kmeans.py.
  *
- * A header of the one library beside vf_hip.h and the vf_hip_*.h family.  Its entries are bound through _lib.KMEANS_SIGNATURES,
- * which _lib.load() applies like the other tables.  Everything the main header says holds here: the conventions at its top
+ * A header of the one library beside vf_hip.h and the vf_hip_*.h family.  Its entries are bound through
+ * _lib.ENTRIES["vf_hip_kmeans.h"], which _lib.load() applies like the other tables.  Everything the main header says holds here: the conventions at its top
  * (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok / VF_ERR_*, vf_last_error()), the
  * comment contract of every entry (arguments, write set, arithmetic and its order, non-finite operands, refusals, not checked),
  * and the ABI version: a new symbol changes no existing one, so it stays 13.
@@ -22,8 +22,8 @@
  * centres, d and k alone: not on R, the strides, the tile constants below or the split of the centres among wavefronts
  * (merging partial winners by (distance, j) is exact).
  */
-#ifndef VF_KMEANS_H
-#define VF_KMEANS_H
+#ifndef VF_HIP_KMEANS_H
+#define VF_HIP_KMEANS_H
 
 #include "vf_hip.h"
 
@@ -167,4 +167,4 @@ int vf_kmeans_seed(const float* x, int64_t ldx, int64_t R, int d, int k, int64_t
 #ifdef __cplusplus
 }
 #endif
-#endif /* VF_KMEANS_H */
+#endif /* VF_HIP_KMEANS_H */

@@ -4,8 +4,8 @@
  * linkage: every pair of mutually nearest clusters belongs to the final tree, so all such pairs of a round merge at once and
  * the tree takes a few dozen data-parallel rounds over a shrinking matrix.  The rounds are driven by variantformer_amd/linkage.py.
  *
- * One of eight headers of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
- * vf_hip_forest.h, vf_hip_topk.h and vf_hip_neighbors.h.  Its entries are bound through _lib.LINKAGE_SIGNATURES, which
+ * One of eight headers of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * vf_hip_forest.h, vf_hip_topk.h and vf_hip_neighbors.h.  Its entries are bound through _lib.ENTRIES["vf_hip_linkage.h"], which
  * _lib.load() applies like the other seven tables, and tests/linkage_cases.py holds their reference and case table.
  * Everything the main header says holds here: the conventions at its top (device pointers owned by the caller, `stream` a
  * hipStream_t, strides in elements, 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write

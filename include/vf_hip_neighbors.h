@@ -2,8 +2,8 @@
  * device, the k most similar rows of one matrix for every row of another (a correlation / cosine k-nearest-neighbour search
  * with no rows x rows buffer), and the dense similarity or distance matrix where it is small enough to exist.
  *
- * One of seven headers of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
- * vf_hip_forest.h and vf_hip_topk.h.  Its entries are bound through _lib.NEIGHBORS_SIGNATURES, which _lib.load() applies like
+ * One of seven headers of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * vf_hip_forest.h and vf_hip_topk.h.  Its entries are bound through _lib.ENTRIES["vf_hip_neighbors.h"], which _lib.load() applies like
  * the other six tables, and tests/neighbors_cases.py holds their references and case table.  Everything the main header says
  * holds here: the conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements,
  * 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write set, arithmetic, non-finite

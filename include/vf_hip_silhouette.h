@@ -1,13 +1,12 @@
-/* vf_silhouette_abi.h -- the entries of libvf_hip.so behind the silhouette coefficient (scikit-learn's silhouette_samples): for
+/* vf_hip_silhouette.h -- the entries of libvf_hip.so behind the silhouette coefficient (scikit-learn's silhouette_samples): for
  * every row the sum of its distances to the members of every cluster, by all pairs for the Euclidean distance and by one fp64
  * product with the clusters' sums for the correlation and cosine distances, and the step from those sums to a, b, s and the
  * nearest other cluster.  Every sum has a stated order and there is no atomic, so two runs are equal bit for bit, a row's result
  * does not depend on the range of rows a call asks for, and numpy restates every entry bit for bit (tests/silhouette_cases.py).
  * The stages are driven by variantformer_amd/validation.py.
  *
- * A header of the one library.  It lives beside the sources, not under include/, and its entries are bound through
- * _lib.SILHOUETTE_ENTRIES, which _lib.load() applies like the *_SIGNATURES tables: the move into include/ and into that family
- * is a rename that waits on two counts pinned by existing tests (DESIGN_HISTORY.md).  Everything include/vf_hip.h says holds
+ * A header of the one library beside vf_hip.h and the vf_hip_*.h family.  Its entries are bound through
+ * _lib.ENTRIES["vf_hip_silhouette.h"], which _lib.load() applies like every other table.  Everything vf_hip.h says holds
  * here: the conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok /
  * VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write set, arithmetic and its order, non-finite
  * operands, refusals, not checked), and the ABI version: a new symbol changes no existing one, so it stays 13.
@@ -26,10 +25,10 @@
  * strides or a tile constant.
  * A NaN result is a NaN; its sign and payload are not part of the contract.
  */
-#ifndef VF_SILHOUETTE_ABI_H
-#define VF_SILHOUETTE_ABI_H
+#ifndef VF_HIP_SILHOUETTE_H
+#define VF_HIP_SILHOUETTE_H
 
-#include "../../include/vf_kmeans.h"
+#include "vf_hip_kmeans.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -59,7 +58,7 @@ extern "C" {
  *   row0, rows  THE QUERY ROWS, 0 <= row0, 0 <= rows, row0 + rows <= R;
  *   S      fp64 [k, >= rows], clusters lds apart.
  * Write set, exactly: S[c * lds + q] for 0 <= c < k, 0 <= q < rows.  x, order and seg are only read, x at columns below d.
- * Arithmetic: D(i, j) is THE DISTANCE of include/vf_kmeans.h between rows i and j: from +0.0f over the columns c = 0 .. d - 1
+ * Arithmetic: D(i, j) is THE DISTANCE of include/vf_hip_kmeans.h between rows i and j: from +0.0f over the columns c = 0 .. d - 1
  * ascending, t = x[i, c] - x[j, c];  p = t * t;  acc = acc + p, every step one individually rounded fp32 operation, NO fused
  * multiply-add.  S[c, i] = the sum over the members j of cluster c, in the order of THE RANGES, of (double)sqrtf(D(i, j)), the
  * square root correctly rounded in fp32, the conversion exact, the additions fp64.  The pair of a row with itself contributes an
@@ -128,4 +127,4 @@ int vf_silhouette_finish(const double* S, int64_t lds, const int32_t* labels, in
 #ifdef __cplusplus
 }
 #endif
-#endif /* VF_SILHOUETTE_ABI_H */
+#endif /* VF_HIP_SILHOUETTE_H */

@@ -6,9 +6,9 @@
  * tall blocks, and a tall block times a small fp64 matrix.  They are driven by variantformer_amd/manifold.py (spectral_embedding),
  * which does the p x p eigenproblems in fp64 on the host.
  *
- * The tenth header of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * The tenth header of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
  * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h, vf_hip_linkage.h and vf_hip_umap.h.  Its entries are bound through
- * _lib.SPECTRAL_SIGNATURES, which _lib.load() applies like the other nine tables, and tests/spectral_cases.py holds their
+ * _lib.ENTRIES["vf_hip_spectral.h"], which _lib.load() applies like the other nine tables, and tests/spectral_cases.py holds their
  * references and case table.  Everything the main header says holds here: the conventions at its top (device pointers owned by
  * the caller, `stream` a hipStream_t, strides in elements, 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every
  * entry (arguments, write set, arithmetic, non-finite operands, refusals), and VF_ABI_VERSION: a new symbol changes no existing

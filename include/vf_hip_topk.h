@@ -1,8 +1,8 @@
 /* vf_hip_topk.h -- the entry of libvf_hip.so behind the ranked cCREs: the k largest values of every row of an attention or
  * contribution map, with their columns, selected on the device.
  *
- * One of six headers of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h and
- * vf_hip_forest.h.  Its entry is bound through _lib.TOPK_SIGNATURES, which _lib.load() applies like the other five tables, and
+ * One of six headers of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h and
+ * vf_hip_forest.h.  Its entry is bound through _lib.ENTRIES["vf_hip_topk.h"], which _lib.load() applies like the other five tables, and
  * tests/topk_cases.py holds its reference and case table (every comparison bit for bit, on poisoned and guarded buffers).
  * Everything the main header says holds here: the conventions at its top (device pointers owned by the caller, `stream` a
  * hipStream_t, strides in elements, 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write

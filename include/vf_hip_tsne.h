@@ -5,9 +5,9 @@
  * and a run can be split at any iteration.  The stages are driven by variantformer_amd/manifold.py (tsne_affinities,
  * tsne_descent, tsne_kl, tsne), which also builds the symmetric graph's CSR arrays and normalises P with torch.
  *
- * The thirteenth header of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * The thirteenth header of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
  * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h, vf_hip_linkage.h, vf_hip_umap.h, vf_hip_spectral.h,
- * vf_hip_umap_transform.h and vf_hip_components.h.  Its entries are bound through _lib.TSNE_SIGNATURES, which _lib.load()
+ * vf_hip_umap_transform.h and vf_hip_components.h.  Its entries are bound through _lib.ENTRIES["vf_hip_tsne.h"], which _lib.load()
  * applies like the other twelve tables, and tests/tsne_cases.py holds their references and case table.  Everything the main
  * header says holds here: the conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in
  * elements, 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write set, arithmetic and its

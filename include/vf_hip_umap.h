@@ -5,8 +5,8 @@
  * epoch began and writes its own row alone, so an epoch has no race, no atomic and one result.  The stages are driven by
  * variantformer_amd/manifold.py, which also builds the symmetric graph's CSR arrays with torch.
  *
- * One of nine headers of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
- * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h and vf_hip_linkage.h.  Its entries are bound through _lib.UMAP_SIGNATURES,
+ * One of nine headers of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h and vf_hip_linkage.h.  Its entries are bound through _lib.ENTRIES["vf_hip_umap.h"],
  * which _lib.load() applies like the other eight tables, and tests/umap_cases.py holds their references and case table.
  * Everything the main header says holds here: the conventions at its top (device pointers owned by the caller, `stream` a
  * hipStream_t, strides in elements, 0 = ok / VF_ERR_*, vf_last_error()), the comment contract of every entry (arguments, write

@@ -6,9 +6,9 @@
  * positions.  The stages are driven by variantformer_amd/manifold.py (fit, UMAPModel.transform), which finds the neighbours with
  * vf_knn_dot and forms the draw counts with torch.
  *
- * The eleventh header of the one library, beside vf_hip.h, vf_hip_next.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
+ * The eleventh header of the one library, beside vf_hip.h, vf_hip_attn_contrib.h, vf_hip_gene_contrib.h, vf_hip_cre_heads.h,
  * vf_hip_forest.h, vf_hip_topk.h, vf_hip_neighbors.h, vf_hip_linkage.h, vf_hip_umap.h and vf_hip_spectral.h.  Its entries are
- * bound through _lib.UMAP_TRANSFORM_SIGNATURES, which _lib.load() applies like the other ten tables, and
+ * bound through _lib.ENTRIES["vf_hip_umap_transform.h"], which _lib.load() applies like the other ten tables, and
  * tests/umap_transform_cases.py holds their references and case table.  Everything the main header says holds here: the
  * conventions at its top (device pointers owned by the caller, `stream` a hipStream_t, strides in elements, 0 = ok / VF_ERR_*,
  * vf_last_error()), the comment contract of every entry, and VF_ABI_VERSION: a new symbol changes no existing one, so the

@@ -1,4 +1,4 @@
-"""Operands and float64 references of vf_attn_contrib (include/vf_hip_next.h), shared by tests/test_attn_contrib_cpu.py,
+"""Operands and float64 references of vf_attn_contrib (include/vf_hip_attn_contrib.h), shared by tests/test_attn_contrib_cpu.py,
 tests/test_attn_contrib_gpu.py and tests/test_contribution_maps_gpu.py.  Importing this module needs no GPU.
 
 The reference forms the contribution VECTORS directly,
@@ -234,10 +234,10 @@ def row_err(got, want) -> float:
     return float((np.abs(got - want).max(axis=-1) / want.max(axis=-1)).max())
 
 
-# ---- the parallel write-set net: one case list for the entries of include/vf_hip_next.h --------------------------------------
+# ---- the parallel write-set net: one case list for the entries of include/vf_hip_attn_contrib.h --------------------------------------
 # tests/write_set_cases.py's machinery (poison patterns, guarded operands, check_write_set) on vf_attn_contrib; its CASES table
 # is a yardstick of the main header and stays as it is, so this list stands beside it.  tests/test_attn_contrib_cpu.py requires
-# every stream-taking declaration of vf_hip_next.h to be named here; tests/test_attn_contrib_gpu.py runs the cases.
+# every stream-taking declaration of vf_hip_attn_contrib.h to be named here; tests/test_attn_contrib_gpu.py runs the cases.
 GRAM_PAD = 8            # gram rows past cu_seqlens_k[n_seq] that must stay untouched
 
 

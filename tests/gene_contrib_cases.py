@@ -197,7 +197,7 @@ def oracle_gene_contributions(monkeypatch, batch, sd, cre_hp, gene_hp, hp, round
 
 
 # ---- the parallel write-set net: one case list for the entry of include/vf_hip_gene_contrib.h ----------------------------------
-# tests/write_set_cases.py's machinery on vf_attn_contrib_self, beside tests/attn_contrib_cases.py's list for vf_hip_next.h.
+# tests/write_set_cases.py's machinery on vf_attn_contrib_self, beside tests/attn_contrib_cases.py's list for vf_hip_attn_contrib.h.
 # tests/test_gene_contrib_cpu.py requires every stream-taking declaration of the header to be named here, entry and wrapper, head
 # summed and per head; tests/test_attn_contrib_self_gpu.py runs the cases.  The wrapper cases read v through a row map into a
 # table whose unnamed rows are poisoned (W.spread_rows); the entry cases read the [:, 2D:] third of a guarded [tokens, 3D] buffer.

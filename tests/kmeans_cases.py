@@ -1,4 +1,4 @@
-"""References, fixtures and the case table of the k-means entries (include/vf_kmeans.h); importable without a GPU.
+"""References, fixtures and the case table of the k-means entries (include/vf_hip_kmeans.h); importable without a GPU.
 
 Two restatements in numpy.  The fp32 one is THE CONTRACT: every operation of the header in the header's order, individually
 rounded, so the device must equal it bit for bit -- labels, distance bits, centre bits, counts, changed, shift, n_iter and the
@@ -26,7 +26,7 @@ from typing import NamedTuple
 import numpy as np
 
 F32, F64 = np.float32, np.float64
-# include/vf_kmeans.h
+# include/vf_hip_kmeans.h
 MAX_K, MAX_R, MAX_D = 4096, 1 << 24, 65536
 ROWS, SPLITS, JT, DC, DC_SMALL = 64, 4, 8, 32, 4
 GROUP = SPLITS * JT

@@ -1,4 +1,4 @@
-"""References, fixtures and the case table of the silhouette entries (variantformer_amd/csrc/vf_silhouette_abi.h); importable
+"""References, fixtures and the case table of the silhouette entries (include/vf_hip_silhouette.h); importable
 without a GPU.
 
 The numpy restatement is THE CONTRACT: every operation of the header in the header's order, individually rounded, so the device
@@ -25,7 +25,7 @@ import numpy as np
 from tests import kmeans_cases as K
 
 F32, F64 = np.float32, np.float64
-# variantformer_amd/csrc/vf_silhouette_abi.h
+# include/vf_hip_silhouette.h
 MAX_K, MAX_R, MAX_D = K.MAX_K, K.MAX_R, K.MAX_D
 RANGES, ROWS, JT, DC_SMALL, DC, DC_WIDE = 4, 64, 8, 4, 32, 64
 NAMES = ["vf_silhouette_finish", "vf_silhouette_sums_dot", "vf_silhouette_sums_l2"]

@@ -1,5 +1,7 @@
 """CPU-side checks of the drop-in boundary: libvf_hip.so builds for gfx950, loads, and exports exactly
-the entry points include/vf_hip.h declares (no compute calls: there is no GPU here)."""
+the entry points the headers under include/ declare (no compute calls: there is no GPU here).  This file owns the generic
+boundary of EVERY header -- it parses, its names are those of its table in _lib.ENTRIES, each is exported, bound and matches its
+prototype type by type, and is declared once; the per-family tests hold what is particular to a family."""
 import ctypes
 import os
 import re
@@ -8,9 +10,13 @@ import pytest
 
 from tests.conftest import REPO
 
+HEADERS = sorted(os.listdir(os.path.join(REPO, "include")))
+N_HEADERS = 16
+N_ENTRIES = 89                  # 53 of vf_hip.h and 36 of the fifteen vf_hip_*.h
 
-def _declared():
-    with open(os.path.join(REPO, "include", "vf_hip.h")) as f:
+
+def _declared(header: str = "vf_hip.h"):
+    with open(os.path.join(REPO, "include", header)) as f:
         src = f.read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
@@ -26,7 +32,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert len(names) >= 12
     for n in names:
         assert hasattr(lib, n), f"{n} declared in vf_hip.h but not exported"
-    assert sorted(_lib.SIGNATURES) == names, "ctypes binding and header disagree"
+    assert sorted(_lib.ENTRIES["vf_hip.h"]) == names, "ctypes binding and header disagree"
     assert _lib.load().vf_version() == _lib.ABI_VERSION
 
 
@@ -77,16 +83,16 @@ def _prototypes(text: str) -> dict:
 
 
 def _bound() -> dict:
-    """name -> (restype, argtypes) of every entry of every *_SIGNATURES dict of _lib.py, read off the loaded library."""
+    """name -> (restype, argtypes) of every entry of every table of _lib.ENTRIES, read off the loaded library."""
     from variantformer_amd import _lib
     lib = _lib.load()
     out = {}
-    for table in sorted(n for n in vars(_lib) if n.endswith("SIGNATURES") and isinstance(getattr(_lib, n), dict)):
-        for name, argtypes in getattr(_lib, table).items():
+    for header, table in sorted(_lib.ENTRIES.items()):
+        for name, argtypes in table.items():
             assert name not in out, f"{name} is bound by two tables"
             fn = getattr(lib, name)
-            assert fn.argtypes is not None, f"_lib.load() does not bind {name} of _lib.{table}"
-            assert list(fn.argtypes) == list(argtypes), f"{name}: load() bound other argtypes than _lib.{table} lists"
+            assert fn.argtypes is not None, f"_lib.load() does not bind {name} of _lib.ENTRIES[{header!r}]"
+            assert list(fn.argtypes) == list(argtypes), f"{name}: load() bound other argtypes than _lib.ENTRIES[{header!r}] lists"
             out[name] = (fn.restype, list(fn.argtypes))
     return out
 
@@ -119,18 +125,44 @@ def _all_declared(texts: dict) -> dict:
 
 def test_every_binding_matches_its_prototype_type_by_type():
     """Parameter by parameter and the return type: a c_int for an int64_t, a c_float for a double or a missing argument would load
-    and run with garbage in a register.  Every header under include/, every *_SIGNATURES table of _lib.py."""
+    and run with garbage in a register.  Every header under include/, every table of _lib.ENTRIES."""
     from variantformer_amd import _lib
     texts = _header_texts()
-    assert len(texts) >= 14 and "vf_hip.h" in texts
+    assert len(texts) == N_HEADERS and "vf_hip.h" in texts
     declared, bound = _all_declared(texts), _bound()
     assert sorted(_prototypes(texts["vf_hip.h"])) == _declared()            # the parser sees what the name test sees
-    assert len(declared) >= 82
+    assert len(declared) == N_ENTRIES
     assert _binding_mismatches(declared, bound) == []
     # load() binds every table the module defines: a table it forgot leaves ctypes' default int arguments in place
-    tables = [n for n in vars(_lib) if n.endswith("SIGNATURES")]
-    assert len(tables) >= 14 and sum(len(getattr(_lib, n)) for n in tables) == len(bound) == len(declared)
+    assert len(_lib.ENTRIES) == N_HEADERS and sum(map(len, _lib.ENTRIES.values())) == len(_lib.SIGNATURES) == len(bound) == len(declared)
+    assert not [n for n in vars(_lib) if n.endswith(("_SIGNATURES", "_ENTRIES"))], "one table: a family adds a key to ENTRIES"
     assert set(_lib._RESTYPES) <= set(bound)
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_header_parses_and_its_names_are_exported_and_bound(header):
+    """The boundary of one header, the same for all sixteen: what tests/test_<family>_cpu.py used to repeat for its own header,
+    each against the headers that existed when it was written."""
+    from variantformer_amd import _lib
+    from variantformer_amd.csrc import build as B
+    texts = _header_texts()
+    assert set(texts) == set(HEADERS) == set(_lib.ENTRIES), "a header under include/ has one table in _lib.ENTRIES, and the reverse"
+    protos = _prototypes(texts[header])
+    names = sorted(protos)
+    assert names and names == _declared(header), "the header parses: every vf_* name before a parenthesis is a prototype"
+    assert sorted(_lib.ENTRIES[header]) == names, f"ctypes binding and {header} disagree"
+    assert any(h.endswith(os.path.join("include", header)) for h in B.HEADERS), "a change of the header rebuilds the library"
+    with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_common.h")) as f:
+        assert f'#include "../../include/{header}"' in f.read(), "the sources see the prototypes they define"
+    lib, bound = ctypes.CDLL(B.build_lib()), _bound()                       # _bound: load() binds each name with the listed argtypes
+    for n in names:
+        assert hasattr(lib, n), f"{n} declared in {header} but not exported"
+        assert bound[n][1] == list(_lib.ENTRIES[header][n]) == list(_lib.SIGNATURES[n])
+    assert _binding_mismatches(protos, {n: bound[n] for n in names}) == []   # type by type, the return type too
+    assert set(_all_declared(texts)) >= set(names)                          # _all_declared: no name is declared in two headers
+    src = re.sub(r"/\*.*?\*/", "", texts[header], flags=re.S)
+    assert bool(re.search(r"#define\s+VF_ABI_VERSION", src)) == (header == "vf_hip.h"), "the version is the main header's"
+    assert _lib.ABI_VERSION == 13 and _lib.load().vf_version() == 13
 
 
 def test_the_type_comparison_names_a_mutated_entry():

@@ -96,12 +96,16 @@ def _side_headers() -> dict:
 
 
 def test_the_stream_table_names_every_stream_taking_entry_of_the_side_headers():
+    """The three stream tables together: the analysis table, and those the k-means and silhouette nets keep beside their cases."""
     from tests import test_analysis_streams_gpu as S
+    from tests import test_kmeans_nets_gpu as KN
+    from tests import test_silhouette_nets_gpu as SN
     headers = _side_headers()
-    assert len(headers) == 13
+    assert len(headers) == 15
     declared = sorted(e for text in headers.values() for e in W.stream_entries(text))
-    assert len(declared) == len(set(declared)) == 29
-    named = [c.entry for c in S.ENTRY_CASES]
+    assert len(declared) == len(set(declared)) == 36
+    named = [c.entry for table in (S.ENTRY_CASES, KN.ENTRY_CASES, SN.ENTRY_CASES) for c in table]
+    assert (len(S.ENTRY_CASES), len(KN.ENTRY_CASES), len(SN.ENTRY_CASES)) == (29, 4, 3)
     assert len(set(named)) == len(named)
     assert sorted(set(declared) - set(named)) == [], "stream-taking entries without a case"
     assert sorted(set(named) - set(declared)) == [], "cases for entries no header declares"

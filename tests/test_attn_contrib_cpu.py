@@ -1,8 +1,7 @@
-"""cCRE contribution maps without a GPU: the vf_attn_contrib boundary (include/vf_hip_next.h parses, every name in it is
-exported and bound through _lib.NEXT_SIGNATURES, every stream-taking declaration has a write-set case in the parallel net, the
+"""cCRE contribution maps without a GPU: the vf_attn_contrib boundary (include/vf_hip_attn_contrib.h parses, every name in it is
+exported and bound through _lib.ENTRIES, every stream-taking declaration has a write-set case in the parallel net, the
 wrapper allocates nothing), every refusal of the entry with the argument named, and -- on the references alone -- that the
 operands of tests/attn_contrib_cases.py tell the contribution norm from four cheaper quantities by far more than the GPU limit."""
-import ctypes
 import inspect
 import os
 import re
@@ -16,36 +15,15 @@ from tests.conftest import REPO
 
 
 def _next_header() -> str:
-    with open(os.path.join(REPO, "include", "vf_hip_next.h")) as f:
+    with open(os.path.join(REPO, "include", "vf_hip_attn_contrib.h")) as f:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 def test_next_header_parses_and_every_name_is_exported_and_bound():
+    """What is this header's own; the boundary every header shares is tests/test_abi_cpu.py's."""
     from variantformer_amd import _lib
-    from variantformer_amd.csrc.build import build_lib
-    text = _next_header()
-    names = _declared(text)
-    assert names == ["vf_attn_contrib"]
-    assert sorted(_lib.NEXT_SIGNATURES) == names, "ctypes binding and vf_hip_next.h disagree"
-    assert not set(_lib.NEXT_SIGNATURES) & set(_lib.SIGNATURES)
-    lib = ctypes.CDLL(build_lib())
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in vf_hip_next.h but not exported"
-    bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for n in names:                                                 # one ctypes type per declared argument
-        args = re.search(rf"\b{n}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, n).argtypes) == len(_lib.NEXT_SIGNATURES[n]) == len([a for a in args.split(",") if a.strip()])
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
-    assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
-    with open(os.path.join(REPO, "include", "vf_hip.h")) as f:
-        main = _declared(f.read())
-    assert not set(names) & set(main), "an entry is declared in one header: moving it to vf_hip.h removes it here"
+    assert sorted(_lib.ENTRIES["vf_hip_attn_contrib.h"]) == ["vf_attn_contrib"], "ctypes binding and vf_hip_attn_contrib.h disagree"
+    assert _lib.ABI_VERSION == 13 and _lib.load().vf_version() == 13
 
 
 def test_every_stream_entry_of_the_next_header_has_a_write_set_case():

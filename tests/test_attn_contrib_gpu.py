@@ -1,7 +1,7 @@
-"""vf_attn_contrib on a real MI355X (include/vf_hip_next.h; operands and float64 references: tests/attn_contrib_cases.py):
+"""vf_attn_contrib on a real MI355X (include/vf_hip_attn_contrib.h; operands and float64 references: tests/attn_contrib_cases.py):
 accuracy of both outputs and of the Gram workspace against the directly formed contribution vectors, independence of a row's
 bits from the rest of the call, the write set under the three poison patterns (the parallel net of the entries declared in
-vf_hip_next.h), the four NaN rules, and one case whose value rows start past element 2^31."""
+vf_hip_attn_contrib.h), the four NaN rules, and one case whose value rows start past element 2^31."""
 import pytest
 import torch
 

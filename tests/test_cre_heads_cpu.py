@@ -1,9 +1,8 @@
 """The tokenizer's per-tissue classifier heads without a GPU: the vf_tissue_heads boundary (include/vf_hip_cre_heads.h parses, its
-one name is exported and bound through _lib.CRE_HEADS_SIGNATURES, disjoint from the other three headers, it has write-set cases
+one name is exported and bound through _lib.ENTRIES, it has write-set cases
 in the parallel net), every refusal of the entry with the argument named, the public surface, and -- on the references alone --
 that the float64 restatement of tests/cre_heads_cases.py reproduces the reference's fixture, that the fixture tells right from
 wrong, and that the kernel-level operands leave the argmax decidable."""
-import ctypes
 import inspect
 import os
 import re
@@ -16,7 +15,6 @@ from tests import write_set_cases as W
 from tests.conftest import REPO
 
 NAME = "vf_tissue_heads"
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h")
 FIXTURE_CASES = ("mean2", "concat2", "ctx1")
 
 
@@ -25,30 +23,13 @@ def _header(name="vf_hip_cre_heads.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_name_is_exported_and_bound():
+    """What is this header's own; the boundary every header shares is tests/test_abi_cpu.py's."""
     from variantformer_amd import _lib
-    from variantformer_amd.csrc.build import build_lib
     text = _header()
-    names = _declared(text)
-    assert names == [NAME]
-    assert sorted(_lib.CRE_HEADS_SIGNATURES) == names, "ctypes binding and vf_hip_cre_heads.h disagree"
-    assert not set(_lib.CRE_HEADS_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.NEXT_SIGNATURES) | set(_lib.GENE_CONTRIB_SIGNATURES))
-    lib = ctypes.CDLL(build_lib())
-    assert hasattr(lib, NAME), f"{NAME} declared in vf_hip_cre_heads.h but not exported"
-    bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    args = re.search(rf"\b{NAME}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-    assert len(getattr(bound, NAME).argtypes) == len(_lib.CRE_HEADS_SIGNATURES[NAME]) == len([a for a in args.split(",") if a.strip()])
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
-    assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
-    for other in OTHER_HEADERS:
-        assert NAME not in _declared(_header(other)), "an entry is declared in one header"
+    assert sorted(_lib.ENTRIES["vf_hip_cre_heads.h"]) == [NAME], "ctypes binding and vf_hip_cre_heads.h disagree"
+    assert _lib.ABI_VERSION == 13 and _lib.load().vf_version() == 13
     for word in ("Write set", "Non-finite operands", "Refused before anything is launched", "Arithmetic"):
         assert word in text, f"the comment contract of {NAME} has no `{word}` part"
 

@@ -1,10 +1,9 @@
 """Enrichment without a GPU: the boundary of include/vf_hip_enrich.h (it parses, its two names are exported and bound through
-_lib.ENRICH_SIGNATURES, disjoint from the other thirteen tables and headers), every refusal of both entries and of the Python
+_lib.ENTRIES), every refusal of both entries and of the Python
 functions with its argument named, the restatement of the tail rule (tests/enrich_cases.py) against exact integer arithmetic on
 the exhaustive grid N <= 12 and on random cells, and against scipy.stats.hypergeom at N = 18 000; Benjamini-Hochberg against
 scipy.stats.false_discovery_control bit for bit; linkage.cut against scipy's cut_tree; membership on hand-made annotations; and
 the planted end-to-end case by scipy alone."""
-import ctypes
 import inspect
 import math
 import os
@@ -21,9 +20,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_enrich_counts", "vf_hypergeom_tail"]
 ARGS = {"vf_enrich_counts": 11, "vf_hypergeom_tail": 14}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                 "vf_hip_neighbors.h", "vf_hip_linkage.h", "vf_hip_umap.h", "vf_hip_spectral.h", "vf_hip_umap_transform.h",
-                 "vf_hip_components.h", "vf_hip_tsne.h")
 
 
 def _header(name="vf_hip_enrich.h") -> str:
@@ -31,22 +27,13 @@ def _header(name="vf_hip_enrich.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.ENRICH_SIGNATURES) == NAMES, "ctypes binding and vf_hip_enrich.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES, _lib.NEIGHBORS_SIGNATURES, _lib.LINKAGE_SIGNATURES, _lib.UMAP_SIGNATURES, _lib.SPECTRAL_SIGNATURES,
-              _lib.UMAP_TRANSFORM_SIGNATURES, _lib.COMPONENTS_SIGNATURES, _lib.TSNE_SIGNATURES)
-    assert not any(set(_lib.ENRICH_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_enrich.h"]) == NAMES, "ctypes binding and vf_hip_enrich.h disagree"
     assert "vf_enrich.hip" in B.SOURCES and any(h.endswith("vf_hip_enrich.h") for h in B.HEADERS)
     assert "vf_enrich.hip" not in B.EXTRA_FLAGS
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_enrich.hip")) as f:
@@ -56,16 +43,8 @@ def test_header_parses_and_its_names_are_exported_and_bound():
     assert "lgamma" not in re.sub(r"//.*", "", source), "the device computes no lgamma"
     atomics = re.findall(r"\b(\w*atomic\w*)\s*\(&?\s*(\w+)", source, flags=re.I)
     assert atomics and all(fn == "atomicAdd" and arg == "bins" for fn, arg in atomics), "integer additions on the LDS bins are the only atomics"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_enrich.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.ENRICH_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "fourteenth header" in text and "contracted into a fused multiply-add" in text
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Not checked"):

@@ -1,9 +1,8 @@
 """The forest evaluator without a GPU: the vf_forest_predict boundary (include/vf_hip_forest.h parses, its one name is exported and
-bound through _lib.FOREST_SIGNATURES, disjoint from the other four headers, it has write-set cases in the parallel net), every
+bound through _lib.ENTRIES, it has write-set cases in the parallel net), every
 refusal of the entry with the argument named, the wrapper that allocates nothing, the converters of variantformer_amd/forest.py
 against scikit-learn, and -- on the references alone -- that the float64 restatement of tests/forest_cases.py reproduces the
 fixture's scikit-learn probabilities and that the fixture tells right from wrong."""
-import ctypes
 import inspect
 import json
 import os
@@ -18,7 +17,6 @@ from tests.conftest import REPO
 from variantformer_amd import forest as Fo
 
 NAME = "vf_forest_predict"
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h")
 
 
 def _header(name="vf_hip_forest.h") -> str:
@@ -26,32 +24,16 @@ def _header(name="vf_hip_forest.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_name_is_exported_and_bound():
+    """What is this header's own; the boundary every header shares is tests/test_abi_cpu.py's."""
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    names = _declared(text)
-    assert names == [NAME]
-    assert sorted(_lib.FOREST_SIGNATURES) == names, "ctypes binding and vf_hip_forest.h disagree"
-    assert not set(_lib.FOREST_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.NEXT_SIGNATURES) | set(_lib.GENE_CONTRIB_SIGNATURES)
-                                              | set(_lib.CRE_HEADS_SIGNATURES))
+    assert sorted(_lib.ENTRIES["vf_hip_forest.h"]) == [NAME], "ctypes binding and vf_hip_forest.h disagree"
     assert "vf_forest.hip" in B.SOURCES and any(h.endswith("vf_hip_forest.h") for h in B.HEADERS)
-    lib = ctypes.CDLL(B.build_lib())
-    assert hasattr(lib, NAME), f"{NAME} declared in vf_hip_forest.h but not exported"
-    bound = _lib.load()
     src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    args = re.search(rf"\b{NAME}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-    assert len(getattr(bound, NAME).argtypes) == len(_lib.FOREST_SIGNATURES[NAME]) == len([a for a in args.split(",") if a.strip()])
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
-    assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
-    for other in OTHER_HEADERS:
-        assert NAME not in _declared(_header(other)), "an entry is declared in one header"
+    assert _lib.ABI_VERSION == 13 and _lib.load().vf_version() == 13
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched"):
         assert word in text, f"the comment contract of {NAME} has no `{word}` part"
     assert {f"VF_FOREST_{k.upper()}": v for k, v in Fo.POSTPROCESSORS.items()} == {

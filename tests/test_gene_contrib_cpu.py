@@ -1,9 +1,8 @@
 """Gene-body contribution maps without a GPU: the vf_attn_contrib_self boundary (include/vf_hip_gene_contrib.h parses, its one
-name is exported and bound through _lib.GENE_CONTRIB_SIGNATURES, disjoint from the other two headers, every stream-taking
+name is exported and bound through _lib.ENTRIES, every stream-taking
 declaration has a write-set case in the parallel net, the wrapper allocates nothing), every refusal of the entry with the
 argument named, the new keyword of the capture and of the public interface, and -- on the references alone -- that the operands
 of tests/gene_contrib_cases.py tell the contribution norm from three cheaper quantities by far more than the GPU limit."""
-import ctypes
 import inspect
 import os
 import re
@@ -23,29 +22,11 @@ def _header(name="vf_hip_gene_contrib.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 def test_header_parses_and_its_name_is_exported_and_bound():
+    """What is this header's own; the boundary every header shares is tests/test_abi_cpu.py's."""
     from variantformer_amd import _lib
-    from variantformer_amd.csrc.build import build_lib
-    text = _header()
-    names = _declared(text)
-    assert names == [NAME]
-    assert sorted(_lib.GENE_CONTRIB_SIGNATURES) == names, "ctypes binding and vf_hip_gene_contrib.h disagree"
-    assert not set(_lib.GENE_CONTRIB_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.NEXT_SIGNATURES))
-    lib = ctypes.CDLL(build_lib())
-    assert hasattr(lib, NAME), f"{NAME} declared in vf_hip_gene_contrib.h but not exported"
-    bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    args = re.search(rf"\b{NAME}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-    assert len(getattr(bound, NAME).argtypes) == len(_lib.GENE_CONTRIB_SIGNATURES[NAME]) == len([a for a in args.split(",") if a.strip()])
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
-    assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
-    for other in ("vf_hip.h", "vf_hip_next.h"):
-        assert NAME not in _declared(_header(other)), "an entry is declared in one header"
+    assert sorted(_lib.ENTRIES["vf_hip_gene_contrib.h"]) == [NAME], "ctypes binding and vf_hip_gene_contrib.h disagree"
+    assert _lib.ABI_VERSION == 13 and _lib.load().vf_version() == 13
 
 
 def test_every_stream_entry_of_the_header_has_a_write_set_case():

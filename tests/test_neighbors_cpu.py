@@ -1,8 +1,7 @@
 """The expression and embedding neighbours without a GPU: the boundary of include/vf_hip_neighbors.h (it parses, its three names
-are exported and bound through _lib.NEIGHBORS_SIGNATURES, disjoint from the other six tables), every refusal with its argument
+are exported and bound through _lib.ENTRIES), every refusal with its argument
 named, the conditions the case table of tests/neighbors_cases.py rests on, its references against scipy and scikit-learn, and
 the host side of variantformer_amd/neighbors.py: matrix building, labels and argument checks."""
-import ctypes
 import inspect
 import os
 import re
@@ -19,7 +18,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_knn_dot", "vf_pairwise_dot", "vf_rows_standardize"]
 ARGS = {"vf_rows_standardize": 9, "vf_knn_dot": 13, "vf_pairwise_dot": 12}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h")
 
 
 def _header(name="vf_hip_neighbors.h") -> str:
@@ -27,33 +25,17 @@ def _header(name="vf_hip_neighbors.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.NEIGHBORS_SIGNATURES) == NAMES, "ctypes binding and vf_hip_neighbors.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES)
-    assert not any(set(_lib.NEIGHBORS_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_neighbors.h"]) == NAMES, "ctypes binding and vf_hip_neighbors.h disagree"
     assert "vf_neighbors.hip" in B.SOURCES and any(h.endswith("vf_hip_neighbors.h") for h in B.HEADERS)
     assert "vf_neighbors.hip" not in B.EXTRA_FLAGS                    # the NaN order needs NaNs honoured: no -fno-honor-nans
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_neighbors.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.NEIGHBORS_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "seven headers" in text
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Order"):

@@ -1,6 +1,5 @@
-"""The silhouette entries without a GPU: the boundary of csrc/vf_silhouette_abi.h (it parses, its three names are exported and
-bound type by type through _lib.SILHOUETTE_ENTRIES, disjoint from every *_SIGNATURES table and declared nowhere under include/),
-every refusal of every entry and of the Python functions, the numpy restatement of tests/silhouette_cases.py against the
+"""The silhouette entries without a GPU: the boundary of include/vf_hip_silhouette.h (it parses, its three names are exported and
+bound type by type through _lib.ENTRIES), every refusal of every entry and of the Python functions, the numpy restatement of tests/silhouette_cases.py against the
 definition on exhaustive tiny cases, and the restatement pinned to scikit-learn's silhouette_samples on the fixtures, whose
 condition for `nearest` is checked first."""
 import ctypes
@@ -23,7 +22,7 @@ CSRC = os.path.join(REPO, "variantformer_amd", "csrc")
 
 
 def _header() -> str:
-    with open(os.path.join(CSRC, "vf_silhouette_abi.h")) as f:
+    with open(os.path.join(REPO, "include", "vf_hip_silhouette.h")) as f:
         return f.read()
 
 
@@ -34,35 +33,25 @@ def test_header_parses_and_its_names_are_exported_and_bound_type_by_type():
     text = _header()
     declared = _prototypes(text)
     assert sorted(declared) == C.NAMES == W.stream_entries(text)
-    assert sorted(_lib.SILHOUETTE_ENTRIES) == C.NAMES, "ctypes binding and vf_silhouette_abi.h disagree"
-    tables = [n for n in vars(_lib) if n.endswith("SIGNATURES")]
-    assert "SILHOUETTE_ENTRIES" not in tables and not any(set(_lib.SILHOUETTE_ENTRIES) & set(getattr(_lib, n)) for n in tables)
-    assert "vf_silhouette.hip" in B.SOURCES and "vf_silhouette_abi.h" in B.HEADERS and "vf_silhouette.hip" not in B.EXTRA_FLAGS
-    with open(os.path.join(CSRC, "vf_common.h")) as f:
-        assert '#include "vf_silhouette_abi.h"' in f.read()
+    assert sorted(_lib.ENTRIES["vf_hip_silhouette.h"]) == C.NAMES, "ctypes binding and vf_hip_silhouette.h disagree"
+    assert "vf_silhouette.hip" in B.SOURCES and "vf_silhouette.hip" not in B.EXTRA_FLAGS
     with open(os.path.join(CSRC, "vf_silhouette.hip")) as f:
         source = f.read()
     assert "#pragma clang fp contract(off)" in source, "the sums' bits hold only without an fma"
     assert "hipDeviceSynchronize" not in source and "hipStreamSynchronize" not in source and "hipMemcpy" not in source, \
         "no entry synchronises the stream or reads anything back"
     assert not re.search(r"\b_*(hip_)?atomic\w*\s*\(", source, flags=re.I), "no atomic: every sum has a stated order"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
     got = {}
     for name in C.NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_silhouette_abi.h but not exported"
         fn = getattr(bound, name)
-        assert list(fn.argtypes) == list(_lib.SILHOUETTE_ENTRIES[name]) and len(fn.argtypes) == ARGS[name], name
+        assert list(fn.argtypes) == list(_lib.SIGNATURES[name]) and len(fn.argtypes) == ARGS[name], name
         got[name] = (fn.restype, list(fn.argtypes))
     assert _binding_mismatches(declared, got) == []
     # the comparison does notice: an int64_t stride bound as int
     broken = dict(got, vf_silhouette_finish=(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + got["vf_silhouette_finish"][1][2:]))
     assert [m.split(":")[0] for m in _binding_mismatches(declared, broken)] == ["vf_silhouette_finish"]
-    for other in sorted(os.listdir(os.path.join(REPO, "include"))):
-        with open(os.path.join(REPO, "include", other)) as f:
-            assert "vf_silhouette" not in f.read(), f"{other}: the entries are declared beside the sources until the rename"
     src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Not checked"):
         assert text.count(word) >= 3, f"an entry's comment contract has no `{word}` part"

@@ -190,7 +190,7 @@ ENTRY_CASES = [S.EntryCase("vf_silhouette_sums_l2", _l2_case), S.EntryCase("vf_s
 
 
 def test_the_stream_cases_name_every_entry_of_the_header():
-    with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_silhouette_abi.h")) as f:
+    with open(os.path.join(REPO, "include", "vf_hip_silhouette.h")) as f:
         assert sorted(W.stream_entries(f.read())) == sorted(c.entry for c in ENTRY_CASES) == C.NAMES
 
 

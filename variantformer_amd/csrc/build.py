@@ -14,11 +14,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["vf_gemm.hip", "vf_attn.hip", "vf_misc.hip", "vf_forest.hip", "vf_topk.hip", "vf_neighbors.hip", "vf_linkage.hip", "vf_umap.hip", "vf_spectral.hip", "vf_umap_transform.hip", "vf_components.hip", "vf_tsne.hip", "vf_enrich.hip", "vf_kmeans.hip", "vf_silhouette.hip", "vf_bpe.cpp", "vf_vcf.cpp", "vf_host.cpp"]
-HEADERS = ["vf_common.h", "vf_silhouette_abi.h"] + [os.path.join("..", "..", "include", h) for h in ("vf_hip.h", "vf_hip_next.h", "vf_hip_gene_contrib.h",
-                                                                                  "vf_hip_cre_heads.h", "vf_hip_forest.h", "vf_hip_topk.h",
-                                                                                  "vf_hip_neighbors.h", "vf_hip_linkage.h", "vf_hip_umap.h",
-                                                                                  "vf_hip_spectral.h", "vf_hip_umap_transform.h", "vf_hip_components.h",
-                                                                                  "vf_hip_tsne.h", "vf_hip_enrich.h", "vf_kmeans.h")]
+INCLUDE = os.path.join("..", "..", "include")
+HEADERS = ["vf_common.h"] + [os.path.join(INCLUDE, h) for h in sorted(os.listdir(os.path.join(HERE, INCLUDE))) if h.endswith(".h")]
 LIB = os.path.join(HERE, "libvf_hip.so")
 ARCH = "gfx950"
 # vf_attn: scores are never NaN by construction (finite inputs, -inf only as a mask), so fmaxf needs no

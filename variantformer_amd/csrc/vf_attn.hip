@@ -2043,7 +2043,7 @@ extern "C" int vf_attn_probs(const void* q, int64_t q_stride, const void* k, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// vf_attn_contrib (include/vf_hip_next.h): the NORM of what key j hands to selected row r through out_proj,
+// vf_attn_contrib (include/vf_hip_attn_contrib.h): the NORM of what key j hands to selected row r through out_proj,
 //   c[r, j] = sum_h P[r, h, j] * Wo[:, h*dh:(h+1)*dh] @ v[j, h, :],   n[r, j] = ||c[r, j]||_2,
 // without forming c.  With S[h, h'] = Wo_h^T Wo_h' (fp32 [H, H, dh, dh], per weights, the caller's):
 //   gram kernel   G[j, h, h'] = v[j, h, :]^T S[h, h'] v[j, h', :]     one block = one head pair h <= h' (S[h, h'] staged in LDS

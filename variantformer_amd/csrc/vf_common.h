@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/vf_hip.h"
-#include "../../include/vf_hip_next.h"
+#include "../../include/vf_hip_attn_contrib.h"
 #include "../../include/vf_hip_gene_contrib.h"
 #include "../../include/vf_hip_cre_heads.h"
 #include "../../include/vf_hip_forest.h"
@@ -17,8 +17,8 @@
 #include "../../include/vf_hip_components.h"
 #include "../../include/vf_hip_tsne.h"
 #include "../../include/vf_hip_enrich.h"
-#include "../../include/vf_kmeans.h"
-#include "vf_silhouette_abi.h"
+#include "../../include/vf_hip_kmeans.h"
+#include "../../include/vf_hip_silhouette.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
@@ -146,8 +146,36 @@ __device__ __forceinline__ f32x4_t gelu_erf4(f32x4_t x) {
 __device__ __forceinline__ float gelu_erf(float x) {
     return gelu_erf4((f32x4_t){x, x, x, x})[0];
 }
+
+// ---- helpers the analysis sources share: integer and bit logic, compares and plain adds only.  A helper with a floating multiply
+// that feeds an add (dist2, attract, ...) stays in its own file, behind that file's `#pragma clang fp contract(off)`: defined
+// here it would be compiled contractable, and the stated bit-exact orders would not survive inlining.
+#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
+#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);               // a butterfly: every lane ends with the same bits
     return v;
 }
+__device__ __forceinline__ bool finite_bits(float d) { return (__float_as_uint(d) & 0x7F800000u) != 0x7F800000u; }
+__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7FC00000u); }
+__device__ __forceinline__ double quiet_nan64() { return __longlong_as_double(0x7FF8000000000000ll); }
+// The 32-bit key of an fp32 bit pattern whose unsigned order is the order the headers state: -Inf lowest, -0 tied with +0, NaN
+// (either sign, any payload) above +Inf.  The smallest key of a value is -Inf's 0x007FFFFF, so a key is never 0 and a pair
+// (key << 32 | anything) is never 0: 0 can mean "none".
+__device__ __forceinline__ uint32_t order_key(uint32_t u) {
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// the hash of the UMAP and k-means headers; the host forms the seeds with it, the device the draws
+__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ float clip4(float v) { return v > 4.f ? 4.f : (v < -4.f ? -4.f : v); }

@@ -152,8 +152,6 @@ __global__ __launch_bounds__(THREADS) void segment_mean_gather_kernel(const floa
     }
 }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
-#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
 
 }  // namespace
 

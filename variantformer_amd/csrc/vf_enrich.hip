@@ -127,8 +127,6 @@ __global__ __launch_bounds__(THREADS) void hypergeom_tail_kernel(const int32_t* 
     steps[at] = r.steps;
 }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
-#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
 
 }  // namespace
 

@@ -1,4 +1,4 @@
-// k-means clustering (include/vf_kmeans.h): the assignment to the nearest centre, the fp64 means, Lloyd's loop with its stop
+// k-means clustering (include/vf_hip_kmeans.h): the assignment to the nearest centre, the fp64 means, Lloyd's loop with its stop
 // decided on the device, and D^2 seeding with integer sampling.  Every sum has the order the header states and there is no
 // atomic, so a run has one result, bit for bit.  Nothing here may contract into an fma (the pragma below); the fp64 divisions
 // are the correctly rounded ones.  The file is built without -fno-honor-nans (csrc/build.py: that flag is vf_attn.hip's): a NaN
@@ -18,9 +18,6 @@ constexpr int UW = VF_KMEANS_UPDATE_WAVES;
 constexpr int UCOLS = VF_KMEANS_UPDATE_COLS;               // == VF_WAVE: one column per lane
 constexpr int RED = VF_KMEANS_RED_THREADS;
 static_assert(ROWS == VF_WAVE && UCOLS == VF_WAVE && ASSIGN_THREADS == 256 && UW * VF_WAVE <= 1024, "the lane mappings below");
-
-__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7FC00000u); }
-__device__ __forceinline__ bool finite_bits(float d) { return (__float_as_uint(d) & 0x7F800000u) != 0x7F800000u; }
 
 // One lane per row, one wavefront per split of the centres; the tiles of GROUP centres x DC columns come through LDS, where a
 // wavefront reads one address.  `labels` may be `prev` (Lloyd's loop): a row's old label is read by the lane that replaces it.
@@ -333,18 +330,9 @@ __global__ __launch_bounds__(RED) void kmeans_select_kernel(const float* __restr
     if (u == 0) rows[t] = row;
 }
 
-uint32_t host_mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
 uint64_t host_hash(int64_t seed, uint32_t t) {
-    const uint32_t a = host_mix32((uint32_t)(uint64_t)seed + 0x9E3779B9u);
-    return ((uint64_t)host_mix32(a ^ (2u * t)) << 32) | (uint64_t)host_mix32(a ^ (2u * t + 1u));
+    const uint32_t a = mix32((uint32_t)(uint64_t)seed + 0x9E3779B9u);
+    return ((uint64_t)mix32(a ^ (2u * t)) << 32) | (uint64_t)mix32(a ^ (2u * t + 1u));
 }
 
 void launch_assign(const float* x, int64_t ldx, int R, int d, const float* cen, int64_t ldc, int k, int32_t* labels, float* dist,
@@ -364,8 +352,6 @@ void launch_update(const float* x, int64_t ldx, int R, int d, const int32_t* lab
                        labels, cen_old, ldc, cen_new, ldn, counts, shift_part, stop);
 }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
-#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
 // the operands every entry shares
 #define VF_KMEANS_COMMON(NAME, CEN)                                                                                       \
     VF_REQUIRE(x, NAME ": null pointer x");                                                                               \

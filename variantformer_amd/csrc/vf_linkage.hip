@@ -13,13 +13,6 @@ namespace {
 constexpr int THREADS = 256;
 constexpr unsigned long long NONE = ~0ull;      // no candidate: above every (key, j), as j < 2^24
 
-// Ascending unsigned order = the header's order: -Inf lowest, -0 tied with +0, NaN above +Inf.
-__device__ __forceinline__ uint32_t ascending_key(uint32_t u) {
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // One block per row: thread t takes the columns t, t + 256, ...; the smallest (key, j) wins, so ties go to the lower j.
 __global__ __launch_bounds__(THREADS) void linkage_nearest_kernel(const float* __restrict__ D, int64_t ld, int m,
                                                                   float* __restrict__ nn_val, int32_t* __restrict__ nn_idx) {
@@ -29,7 +22,7 @@ __global__ __launch_bounds__(THREADS) void linkage_nearest_kernel(const float* _
     unsigned long long best = NONE;
     for (int j = threadIdx.x; j < m; j += THREADS) {
         if (j == i) continue;
-        const unsigned long long c = ((unsigned long long)ascending_key(row[j]) << 32) | (uint32_t)j;
+        const unsigned long long c = ((unsigned long long)order_key(row[j]) << 32) | (uint32_t)j;
         best = c < best ? c : best;
     }
 #pragma unroll
@@ -133,7 +126,6 @@ __global__ __launch_bounds__(THREADS) void linkage_contract_kernel(const float* 
     }
 }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
 
 }  // namespace
 

@@ -14,16 +14,9 @@ static_assert(BM == 64 && BN == 64 && BK % 2 == 0 && THREADS % BK == 0, "the wav
 static_assert(BN == VF_WAVE && VF_TOPK_MAX_K <= VF_WAVE, "one lane per tile column and per rank");
 static_assert((BM + BN) * LDT >= BM * BN, "the score tile reuses the operand tiles' LDS");
 
-// vf_topk.hip's key: its unsigned order is the header's order.  NaN above +Inf, -0 tied with +0; never 0.
-__device__ __forceinline__ uint32_t rank_key(uint32_t u) {
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // (key, 2^32 - 1 - j): larger = ranks first, the lower j among equal keys.  nj == 0 marks an empty slot (j < 2^31, so no row has it).
 __device__ __forceinline__ unsigned long long rank_pair(uint32_t vbits, uint32_t nj) {
-    return nj ? ((unsigned long long)rank_key(vbits) << 32) | nj : 0ull;
+    return nj ? ((unsigned long long)order_key(vbits) << 32) | nj : 0ull;
 }
 
 // The 64 x 64 tile of s(q0 + ., j0 + .) into S (row-major, BN words per row; S overlays the operand tiles).  Every thread of
@@ -188,12 +181,6 @@ __global__ __launch_bounds__(THREADS) void pairwise_dot_kernel(const float* __re
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // One wave per row, 4 rows per block.  No __restrict__: z may be x.
 __global__ __launch_bounds__(THREADS) void rows_standardize_kernel(const float* x, int64_t ldx, int64_t R, int d, int center,
                                                                    float* z, int64_t ldz, float* norm) {
@@ -232,7 +219,6 @@ __global__ __launch_bounds__(THREADS) void rows_standardize_kernel(const float* 
     if (norm && lane == 0) norm[r] = flat ? 0.f : nrm;
 }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
 
 // The checks vf_knn_dot and vf_pairwise_dot share; `out` is the name of the width ldo is held against.
 int check_operands(const char* fn, const float* q, int64_t ldq, int64_t Rq, const float* y, int64_t ldy, int64_t Ry, int d,

@@ -1,4 +1,4 @@
-// Silhouette sums (vf_silhouette_abi.h): every query row's summed distance to the members of every cluster, by all pairs for the
+// Silhouette sums (vf_hip_silhouette.h): every query row's summed distance to the members of every cluster, by all pairs for the
 // Euclidean distance and through the clusters' fp64 column sums for the correlation and cosine distances, and the step from the
 // sums to a, b, s and the nearest other cluster.  Every sum has the order the header states and there is no atomic, so a run has
 // one result, bit for bit.  Nothing here may contract into an fma (the pragma below); __builtin_sqrtf and the fp64 divisions are
@@ -16,8 +16,6 @@ constexpr int GROUP = W * JT;                              // members (or cluste
 constexpr int THREADS = ROWS * W;
 static_assert(ROWS == VF_WAVE && THREADS <= 1024 && W >= 1, "the lane mappings below");
 
-__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7FC00000u); }
-__device__ __forceinline__ double quiet_nan64() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 // the segment of cluster c, clamped to 0 .. n and never backwards: a malformed CSR reads nothing outside `order`
 __device__ __forceinline__ void segment(const int64_t* __restrict__ seg, int c, int n, int& lo, int& nc) {
@@ -251,8 +249,6 @@ int spread(int row_blocks, int units) {
     return want < 1 ? 1 : (want > units ? units : want);
 }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
-#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
 // the row range every entry shares
 #define VF_SILHOUETTE_RANGE(NAME)                                                                                                          \
     VF_REQUIRE(k >= 1 && k <= VF_SILHOUETTE_MAX_K, NAME ": k=%d outside 1 .. %d", k, VF_SILHOUETTE_MAX_K);                                  \

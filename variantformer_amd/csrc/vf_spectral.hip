@@ -146,8 +146,6 @@ __global__ __launch_bounds__(THREADS) void tall_mul_kernel(const float* __restri
     Out[i * ldo + c] = (float)s;
 }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
-#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
 
 int64_t gram_chunk(int64_t R) {
     const int64_t span = (int64_t)TILE * VF_TALL_GRAM_MAX_BLOCKS;

@@ -5,13 +5,7 @@
 
 namespace {
 
-// The 32-bit key whose unsigned order is the header's order: NaN (either sign, any payload) above +Inf, -0 tied with +0.
-// The smallest key of a value is -Inf's 0x007FFFFF, so a pair (key << 32 | VF_TOPK_MAX_N - column) is never 0: 0 = no column.
-__device__ __forceinline__ uint32_t topk_key(uint32_t u) {
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// order_key (vf_common.h): the smallest key is -Inf's 0x007FFFFF, so a pair (key << 32 | VF_TOPK_MAX_N - column) is never 0: 0 = no column.
 
 // One block = one wave = one row.  Round i finds the largest pair below round i - 1's: lane l scans the columns l, l + 64, ...
 // of the staged keys, the butterfly leaves the winner in every lane, and lane i keeps it.  The pairs of a row are distinct,
@@ -29,7 +23,7 @@ __global__ __launch_bounds__(64) void topk_rows_kernel(const float* __restrict__
         len = len < 0 ? 0 : (len > n ? n : len);
     }
     const uint32_t* xr = reinterpret_cast<const uint32_t*>(x) + r * ldx;
-    for (int c = lane; c < len; c += 64) keys[c] = topk_key(xr[c]);
+    for (int c = lane; c < len; c += 64) keys[c] = order_key(xr[c]);
     __syncthreads();
     unsigned long long prev = ~0ull, mine = 0ull;                     // every pair is below ~0: its low word is at most 16384
     for (int i = 0; i < k; ++i) {

@@ -16,7 +16,6 @@ constexpr int PER_LANE = (VF_TSNE_MAX_M + VF_WAVE) / VF_WAVE;       // 4 entries
 constexpr int TILE = VF_TSNE_TILE;
 constexpr int ATTR_THREADS = 64;           // one vertex per thread: small blocks spread a few thousand vertices over the CUs
 
-__device__ __forceinline__ bool finite_bits(float d) { return (__float_as_uint(d) & 0x7F800000u) != 0x7F800000u; }
 
 // One wavefront per row; entry t lives on lane t mod 64 and stays in registers across the search.
 __global__ __launch_bounds__(THREADS) void tsne_perplexity_kernel(const int32_t* __restrict__ idx, int64_t ld_idx,
@@ -299,8 +298,6 @@ void launch_attraction(const int64_t* rowptr, const int32_t* col, const float* p
         case 4 * 4 + 3: CALL(4, 3); break;              \
     }
 
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
-#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
 
 }  // namespace
 

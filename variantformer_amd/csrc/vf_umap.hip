@@ -16,14 +16,6 @@ constexpr int WALK = 8;                    // entries whose sample counts are lo
 constexpr int NEG = 5;                     // negative vertices whose positions are loaded together: the default rate
 constexpr int LAYOUT_THREADS = 64;          // one vertex per thread: small blocks spread a few thousand vertices over the CUs
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);       // a butterfly: every lane ends with the same bits
-    return v;
-}
-
-__device__ __forceinline__ bool finite_bits(float d) { return (__float_as_uint(d) & 0x7F800000u) != 0x7F800000u; }
-
 // One wavefront per row, lane t holds entry t.
 __global__ __launch_bounds__(THREADS) void umap_smooth_knn_kernel(const int32_t* __restrict__ idx, int64_t ld_idx,
                                                                   const float* __restrict__ dist, int64_t ld_dist, int R, int m,
@@ -101,17 +93,6 @@ __global__ __launch_bounds__(THREADS) void umap_union_kernel(const int32_t* __re
         w[e] = (a + b) - a * b;
     }
 }
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ float clip4(float v) { return v > 4.f ? 4.f : (v < -4.f ? -4.f : v); }
 
 template <int DIM>
 __device__ __forceinline__ float dist2(const float (&y)[DIM], const float (&o)[DIM]) {
@@ -213,17 +194,6 @@ void launch_layout(const int64_t* rowptr, const int32_t* col, const int32_t* sam
                        stream, rowptr, col, samples, nnz, R, Yin, Yout, ld, n, N, a, b, gamma, alpha, rate, seed_n);
 }
 
-uint32_t host_mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
-#define VF_ALIGNED8(p) ((uintptr_t)(p) % 8 == 0)
 
 }  // namespace
 
@@ -303,13 +273,13 @@ extern "C" int vf_umap_layout(const int64_t* rowptr, const int32_t* col, const i
     VF_REQUIRE(epoch_end <= N, "vf_umap_layout: epoch_end=%d is above N=%d", epoch_end, N);
     VF_REQUIRE(negative_sample_rate >= 0, "vf_umap_layout: negative_sample_rate=%d must not be negative", negative_sample_rate);
     if (R == 0 || epoch_begin == epoch_end) return VF_OK;
-    const uint32_t seed0 = host_mix32((uint32_t)(uint64_t)seed + 0x9E3779B9u);
+    const uint32_t seed0 = mix32((uint32_t)(uint64_t)seed + 0x9E3779B9u);
     for (int n = epoch_begin; n < epoch_end; ++n) {
         const bool even = ((n - epoch_begin) & 1) == 0;
         const float* Yin = even ? Y0 : Y1;
         float* Yout = even ? Y1 : Y0;
         const float alpha = learning_rate * (1.f - (float)n / (float)N);
-        const uint32_t seed_n = host_mix32(seed0 ^ (uint32_t)n);
+        const uint32_t seed_n = mix32(seed0 ^ (uint32_t)n);
 #define VF_UMAP_DIM(D)                                                                                                              \
     case D:                                                                                                                         \
         launch_layout<D>(rowptr, col, samples, nnz, (int)R, Yin, Yout, ld, n, N, a, b, gamma, alpha, negative_sample_rate, seed_n, \

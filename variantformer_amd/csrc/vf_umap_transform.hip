@@ -16,14 +16,6 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int ROWS_PER_BLOCK = THREADS / VF_WAVE;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);       // vf_umap_smooth_knn's butterfly: the same bits in every lane
-    return v;
-}
-
-__device__ __forceinline__ bool finite_bits(float d) { return (__float_as_uint(d) & 0x7F800000u) != 0x7F800000u; }
-
 // the value lane `src` holds, in every lane; src is the same in every lane
 __device__ __forceinline__ float from_lane(float v, int src) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), __builtin_amdgcn_readfirstlane(src)));
@@ -98,17 +90,6 @@ __global__ __launch_bounds__(THREADS) void umap_init_transform_kernel(const int3
         if (lane == 0) Yq[(int64_t)i * ldq + c] = acc;
     }
 }
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ float clip4(float v) { return v > 4.f ? 4.f : (v < -4.f ? -4.f : v); }
 
 template <int DIM>
 __device__ __forceinline__ float dist2(const float (&y)[DIM], const float (&o)[DIM]) {
@@ -228,16 +209,6 @@ __global__ __launch_bounds__(THREADS) void umap_layout_transform_kernel(const in
     }
 }
 
-uint32_t host_mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7FEB352Du;
-    x ^= x >> 15;
-    x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
-#define VF_ALIGNED4(p) ((uintptr_t)(p) % 4 == 0)
 
 }  // namespace
 
@@ -326,7 +297,7 @@ extern "C" int vf_umap_layout_transform(const int32_t* idx, int64_t ld_idx, cons
     VF_REQUIRE(negative_sample_rate <= (1 << 20), "vf_umap_layout_transform: negative_sample_rate=%d is above 2^20", negative_sample_rate);
     if (Rq == 0 || epoch_begin == epoch_end) return VF_OK;
     VF_REQUIRE(R >= 1, "vf_umap_layout_transform: R=%ld training rows: the queries have nothing to be placed among", (long)R);
-    const uint32_t seed0 = host_mix32((uint32_t)(uint64_t)seed + 0x9E3779B9u);
+    const uint32_t seed0 = mix32((uint32_t)(uint64_t)seed + 0x9E3779B9u);
     const float lr4 = learning_rate / 4.f;
     const dim3 grid((unsigned)((Rq + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK));
     for (int n0 = epoch_begin; n0 < epoch_end; n0 += VF_UMAP_TRANSFORM_EPOCHS_PER_LAUNCH) {

@@ -5,7 +5,7 @@ within UMAP clusters", and the assignment of a second individual's rows to the c
   KMeansModel.predict(q)       the nearest fitted centre of every query row: an assignment alone;
   random_rows / seed_rows      the two starts: k distinct rows from a counter hash, or plain D^2 seeding on the device.
 
-Everything runs on the device through the four entries of include/vf_kmeans.h: the squared distance is a
+Everything runs on the device through the four entries of include/vf_hip_kmeans.h: the squared distance is a
 running fp32 sum of (x - c)^2 in column order with no fma, the means are fp64 sums in a stated order, all iterations of a run
 come from one loop inside the library and the stop is decided on the device.  There is no atomic, so a run has one result, bit
 for bit, and tests/kmeans_cases.py restates every entry in numpy.  It is linear in the rows: 262 144 x 64 with 1 024 centres
@@ -43,7 +43,7 @@ def _mix32(x: int) -> int:
 
 
 def hash64(seed: int, t: int) -> int:
-    """hash(seed, t) of include/vf_kmeans.h: 64 bits from two words of the mixer."""
+    """hash(seed, t) of include/vf_hip_kmeans.h: 64 bits from two words of the mixer."""
     a = _mix32((int(seed) & _MASK) + 0x9E3779B9)
     return (_mix32(a ^ (2 * t)) << 32) | _mix32(a ^ (2 * t + 1))
 

@@ -604,7 +604,7 @@ def attn_probs(q: torch.Tensor, k: torch.Tensor, cu_rows: torch.Tensor, cu_k: to
 def attn_contrib(v: torch.Tensor, s_gram: torch.Tensor, probs: torch.Tensor, cu_rows: torch.Tensor, cu_k: torch.Tensor,
                  max_rows: int, max_k: int, n_heads: int, head_dim: int, gram: torch.Tensor, out: torch.Tensor,
                  per_head: bool = False, family: str = ""):
-    """Value-weighted norms beside an attention map (vf_attn_contrib, include/vf_hip_next.h): out[r, j] = || sum_h P[r, h, j] *
+    """Value-weighted norms beside an attention map (vf_attn_contrib, include/vf_hip_attn_contrib.h): out[r, j] = || sum_h P[r, h, j] *
     Wo_h v[j, h] ||_2, or per head out[r * H + h, j] = P[r, h, j] * || Wo_h v[j, h] ||_2.  v [tk, >= H*dh] 16-bit row-strided view
     (the value rows the attention kernel reads); s_gram fp32 [H, H, dh, dh] = Wo_h^T Wo_h' (per weights); probs fp32 [R * H, >=
     max_k] = ops.attn_probs(per_head=True) of the same rows and grouping.  The caller owns every buffer, and nothing is made
@@ -1232,7 +1232,7 @@ def hypergeom_tail(count: torch.Tensor, size: torch.Tensor, csize: torch.Tensor,
     return log_p, tail, steps
 
 
-# include/vf_kmeans.h: VF_KMEANS_MAX_K, _MAX_R, _MAX_D, _ROWS, _UPDATE_COLS, _RED_THREADS
+# include/vf_hip_kmeans.h: VF_KMEANS_MAX_K, _MAX_R, _MAX_D, _ROWS, _UPDATE_COLS, _RED_THREADS
 KMEANS_MAX_K, KMEANS_MAX_R, KMEANS_MAX_D, KMEANS_ROWS, KMEANS_UPDATE_COLS, KMEANS_RED_THREADS = 4096, 1 << 24, 65536, 64, 64, 256
 
 
@@ -1258,7 +1258,7 @@ def _kmeans_operands(x: torch.Tensor, cen: torch.Tensor, name: str = "cen"):
 
 
 def kmeans_assign(x: torch.Tensor, cen: torch.Tensor, *, labels: torch.Tensor, dist: torch.Tensor, family: str = ""):
-    """The nearest centre of every row (vf_kmeans_assign, include/vf_kmeans.h).  x fp32 [R, d] and cen fp32 [k, d] row-strided,
+    """The nearest centre of every row (vf_kmeans_assign, include/vf_hip_kmeans.h).  x fp32 [R, d] and cen fp32 [k, d] row-strided,
     only read; labels int32 [R] and dist fp32 [R] contiguous.  The squared distance is a running fp32 sum of (x - c)^2 over the
     columns in ascending order, every operation rounded once, no fma; the smallest wins, ties to the lower centre, a NaN never;
     a row with no winner has label -1 and dist NaN.  The caller owns every buffer and nothing is made here.  Returns
@@ -1279,7 +1279,7 @@ def kmeans_assign(x: torch.Tensor, cen: torch.Tensor, *, labels: torch.Tensor, d
 
 def kmeans_update(x: torch.Tensor, labels: torch.Tensor, cen_old: torch.Tensor, *, cen_new: torch.Tensor, counts: torch.Tensor,
                   family: str = ""):
-    """The fp64 mean of every cluster's rows (vf_kmeans_update, include/vf_kmeans.h).  x fp32 [R, d] row-strided and labels int32
+    """The fp64 mean of every cluster's rows (vf_kmeans_update, include/vf_hip_kmeans.h).  x fp32 [R, d] row-strided and labels int32
     [R], only read (a label outside 0 .. k - 1 belongs to no centre); cen_old fp32 [k, d] row-strided; cen_new fp32 [k, d]
     row-strided, which may be cen_old itself; counts int32 [k].  The sums run over VF_KMEANS_UPDATE_WAVES contiguous row ranges
     in ascending row order and are added in range order; a centre without members keeps cen_old's bits.  No atomic: one result,
@@ -1303,7 +1303,7 @@ def kmeans_update(x: torch.Tensor, labels: torch.Tensor, cen_old: torch.Tensor, 
 def kmeans_lloyd(x: torch.Tensor, cen: torch.Tensor, *, max_iter: int, tol_abs: float, resume: bool = False, labels: torch.Tensor,
                  dist: torch.Tensor, prev_labels: torch.Tensor, counts: torch.Tensor, n_iter: torch.Tensor, shift: torch.Tensor,
                  changed: torch.Tensor, work: torch.Tensor, family: str = ""):
-    """Up to max_iter iterations of Lloyd's loop and a last assignment (vf_kmeans_lloyd, include/vf_kmeans.h), from one loop inside
+    """Up to max_iter iterations of Lloyd's loop and a last assignment (vf_kmeans_lloyd, include/vf_hip_kmeans.h), from one loop inside
     the library with the stop decided on the device: scikit-learn's _kmeans_single_lloyd.  x fp32 [R, d] row-strided, only read;
     cen fp32 [k, d] row-strided: in, the start; out, the result.  labels int32 [R] and dist fp32 [R]: the last assignment;
     prev_labels int32 [R]: the labels of the last iteration that ran (read with resume=True); counts int32 [k]; n_iter int32 [1];
@@ -1339,7 +1339,7 @@ def kmeans_lloyd(x: torch.Tensor, cen: torch.Tensor, *, max_iter: int, tol_abs: 
 
 def kmeans_seed(x: torch.Tensor, k: int, seed: int, *, rows: torch.Tensor, cen: torch.Tensor, mind: torch.Tensor, work: torch.Tensor,
                 family: str = ""):
-    """Plain D^2 seeding (vf_kmeans_seed, include/vf_kmeans.h): k rows of x, each drawn with probability proportional to its
+    """Plain D^2 seeding (vf_kmeans_seed, include/vf_hip_kmeans.h): k rows of x, each drawn with probability proportional to its
     squared distance to the nearest row drawn before, in exact integer arithmetic from a counter hash of (seed, step).  x fp32
     [R, d] row-strided, only read; rows int32 [k]: the chosen rows; cen fp32 [k, d] row-strided: copies of them; mind fp32 [R];
     work a contiguous buffer of at least kmeans_seed_work_bytes(R) bytes.  One result, bit for bit, which numpy restates
@@ -1360,7 +1360,7 @@ def kmeans_seed(x: torch.Tensor, k: int, seed: int, *, rows: torch.Tensor, cen: 
     return rows, cen
 
 
-# csrc/vf_silhouette_abi.h: VF_SILHOUETTE_MAX_K, _MAX_R, _MAX_D (k-means'), _RANGES
+# include/vf_hip_silhouette.h: VF_SILHOUETTE_MAX_K, _MAX_R, _MAX_D (k-means'), _RANGES
 SILHOUETTE_MAX_K, SILHOUETTE_MAX_R, SILHOUETTE_MAX_D, SILHOUETTE_RANGES = KMEANS_MAX_K, KMEANS_MAX_R, KMEANS_MAX_D, 4
 
 
@@ -1390,7 +1390,7 @@ def _silhouette_operands(x, order, seg, S, row0, rows):
 
 def silhouette_sums_l2(x: torch.Tensor, order: torch.Tensor, seg: torch.Tensor, row0: int, rows: int, *, S: torch.Tensor, family: str = ""):
     """Every query row's summed Euclidean distance to the members of every cluster, by all pairs (vf_silhouette_sums_l2,
-    csrc/vf_silhouette_abi.h).  x fp32 [R, d] row-strided, only read; order int32 [n] and seg int64 [k + 1]: the clusters as a CSR of
+    include/vf_hip_silhouette.h).  x fp32 [R, d] row-strided, only read; order int32 [n] and seg int64 [k + 1]: the clusters as a CSR of
     rows (the rows with a label, sorted by label and ascending within one; the offsets); the query rows are [row0, row0 + rows);
     S fp64 [k, rows] row-strided: S[c, i - row0].  The squared distance is k-means' fp32 chain, then a correctly rounded square
     root and an fp64 sum over the members in VF_SILHOUETTE_RANGES contiguous ranges: one result, bit for bit, the same for any row
@@ -1411,7 +1411,7 @@ def silhouette_sums_l2(x: torch.Tensor, order: torch.Tensor, seg: torch.Tensor, 
 def silhouette_sums_dot(z: torch.Tensor, order: torch.Tensor, seg: torch.Tensor, labels: torch.Tensor, row0: int, rows: int, *,
                         S: torch.Tensor, work: torch.Tensor, family: str = ""):
     """Every query row's summed distance 1 - z_i . z_j to the members of every cluster other than itself, from the clusters' fp64
-    column sums (vf_silhouette_sums_dot, csrc/vf_silhouette_abi.h): linear in the rows.  z fp32 [R, d] row-strided: standardised
+    column sums (vf_silhouette_sums_dot, include/vf_hip_silhouette.h): linear in the rows.  z fp32 [R, d] row-strided: standardised
     rows, only read; order, seg as in silhouette_sums_l2; labels int32 [R] (a value outside 0 .. k - 1: no label); S fp64 [k, rows]
     row-strided; work a contiguous buffer of at least silhouette_dot_work_bytes(d, k) bytes, which afterwards holds the column
     sums.  Two launches; every sum in a stated order: one result, bit for bit.  The caller owns every buffer and
@@ -1434,7 +1434,7 @@ def silhouette_sums_dot(z: torch.Tensor, order: torch.Tensor, seg: torch.Tensor,
 
 def silhouette_finish(S: torch.Tensor, labels: torch.Tensor, seg: torch.Tensor, row0: int, rows: int, *, a: torch.Tensor, b: torch.Tensor,
                       s: torch.Tensor, nearest: torch.Tensor, family: str = ""):
-    """From the sums to the silhouette of the rows [row0, row0 + rows) (vf_silhouette_finish, csrc/vf_silhouette_abi.h).  S fp64
+    """From the sums to the silhouette of the rows [row0, row0 + rows) (vf_silhouette_finish, include/vf_hip_silhouette.h).  S fp64
     [k, rows] row-strided: what either sums entry wrote for the same range; labels int32 [R]; seg int64 [k + 1]; a, b, s fp64 [R]
     and nearest int32 [R], written at the range alone: the mean distance to the own cluster's other members, the smallest mean to
     another non-empty cluster (ties to the lower one, a NaN never), (b - a) / max(a, b), and that cluster.  The caller owns

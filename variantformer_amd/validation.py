@@ -6,7 +6,7 @@ linkage.cut and expression_enrichment leave to the user.
   silhouette_sweep(x, ks, method)         cluster at every k of `ks` (k-means, or one Ward tree cut once per k) and score each.
 
 Definitions are scikit-learn's silhouette_samples.  Everything runs on the device through the three entries of
-csrc/vf_silhouette_abi.h.  metric="euclidean" needs all pairs: every row against every member of every cluster,
+include/vf_hip_silhouette.h.  metric="euclidean" needs all pairs: every row against every member of every cluster,
 the squared distance k-means' fp32 chain, then a correctly rounded square root and fp64 sums in a stated order.
 metric="correlation" / "cosine" is linear: the sum of 1 - z_i . z_j over a cluster is n_c - z_i . M_c with M_c the cluster's
 fp64 column sums of the standardised rows, O(rows k d), never all pairs.  There is no atomic, so a run has one result, bit for
